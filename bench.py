@@ -6,9 +6,14 @@ B=8 per GPU, synthetic inputs resident in HBM.
     python bench.py --gpus 1 --steps K --warmup W
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     python bench.py --size 512 --batch 4 --inference          # BASELINE.json configs[4]: 512x512 inference-only generator path
+    python bench.py --gpus 1 --steps K --warmup W --full      # + roofline, CPU baseline, other precisions and configurations
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR     # + what the last timed step (from the initial state) computed, as DIR/*.npy
 
 Rank 0 prints ONE JSON line.  A step = pack + forward + backward + (flat RCCL all-reduce, N > 1) + clip + Adam, replayed
 as hipGraphs (mrfa_amd/graph.py; `--no-graph` launches every kernel eagerly, with DistributedDataParallel for N > 1).
+A plain run sets up, warms up, times the steps and prints the line; everything else it can measure runs only with `--full`
+(`roofline`, `cpu_baseline`, `forward_only`, the bf16x3 / native-fp32 matrix paths and the config 4 / config 5 records; the
+`--no-*` options then leave single parts out).
 `roofline` is measured live with HIP events around every launch of the dominant kernel (the 128x128 implicit-GEMM convolution
 tile, forward + data-gradient launches: `conv_bf16x6_kernel` on the bf16 matrix pipe with exactly split fp32 operands by default,
 `conv_mfma_kernel<128,128,...>` on the native fp32 matrix pipe with `--mfma f32`): inside the timed region for eager launches,
@@ -64,6 +69,56 @@ def init_weights(model):
                 sd[k] = torch.tensor([1.0, 0.0, 0.0, 0.0, 1.0, 0.0]) + sd[k] * 0.1
         model.bg_predictor.load_state_dict(sd)
         out.update({"bg_predictor." + k: v for k, v in sd.items()})
+    return out
+
+
+# --dump-outputs writes at most this many float32 elements in all (60 MB), shared evenly by the arrays of one dump
+DUMP_BUDGET_ELEMS = 15 * 10 ** 6
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: every array as out_dir/<name>.npy in float32.  An array above its share of DUMP_BUDGET_ELEMS is flattened and cut
+    to the elements at that many positions drawn from a fixed seed: the same positions in every run with the same arguments."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_BUDGET_ELEMS // len(arrays)
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if t.numel() > cap:
+            idx = torch.randint(t.numel(), (cap,), generator=torch.Generator().manual_seed(0))
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+
+
+def training_state(model, opt) -> list:
+    """every tensor a training step reads and updates: weights, buffers (BatchNorm running statistics) and the optimizer's state"""
+    ts = list(model.state_dict().values()) + [t for st in opt.state.values() for t in st.values() if torch.is_tensor(t)]
+    if hasattr(opt, "dev_state"):                     # FlatAdam: step counts and learning rates of its parameter groups
+        ts.append(opt.dev_state)
+    return ts
+
+
+def restore_state(model, opt, snapshot) -> None:
+    """put the training state back to `snapshot` (pairs of (tensor, copy) from before the first step), in place: the captured graphs keep
+    their addresses.  Optimizer state created after the snapshot (torch.optim.Adam's, lazily) is zeroed, which is Adam's fresh state."""
+    saved = {(t.data_ptr(), t.numel()) for t, _ in snapshot}       # (state_dict() returns new alias objects on every call)
+    with torch.no_grad():
+        for t, c in snapshot:
+            t.copy_(c)
+        for t in training_state(model, opt):
+            if (t.data_ptr(), t.numel()) not in saved:
+                t.zero_()
+
+
+def step_outputs(model, loss, gen=None) -> dict:
+    """what the training step computes that is the same in every run from the same weights and inputs: the loss, the generated frames
+    (when the step exposes them) and the updated BatchNorm running statistics.  Not its gradients, nor the Adam-updated weights: float
+    atomics change the summation order from run to run, and the train-mode backward of this model turns that into a percent-level
+    spread of the gradients (GraphedTrainStep.verify's eager band: two passes at identical weights differ by ~1 %)."""
+    out = {"loss": loss.reshape(1)}
+    if gen is not None:
+        out["generated"] = gen
+    out["buffers"] = torch.cat([b.detach().reshape(-1).float() for b in model.buffers() if b.is_floating_point()])
     return out
 
 
@@ -192,6 +247,8 @@ def run_inference(a, emit=True):
             tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             dt = float(tmax.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"generated": out})
     ms = 1e3 * dt / a.steps
     scale = (size / 256.0) ** 2
     gflop = (scale * (362.73 - 8.59) + 8.59 * scale * scale) * B          # conv FLOPs x (size/256)^2, correlation GEMM x (size/256)^4
@@ -504,9 +561,19 @@ def main(rank_body=None, script=None, argv=None, child_argv=None):
                          "(the line then says config.launch = eager)")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
                     help="mrfa_set_tuning knob (kernel selection only, never results), repeatable: A/B runs on one box, e.g. --tune conv_halo=0")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure roofline, cpu_baseline, forward_only, the bf16x3 / native-fp32 matrix paths and "
+                         "the config 4 / config 5 records (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, 60 MB at most: large arrays as a fixed, seeded sample); "
+                         "training: that step starts from the initial weights and optimizer state, so that its inputs are the same in every run")
     a = ap.parse_args(argv)
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
+    if not a.full:              # a plain run: setup, warm-up, the timed steps, the line -- every extra measurement hangs off these three
+        a.no_roofline = a.no_forward = a.no_cpu_baseline = True
     # ---- ranks.  Under torch.distributed.run (the driver's N > 1 command) WORLD_SIZE is set and must equal --gpus; a bare
     # `python bench.py --gpus N` starts its N ranks itself, BEFORE anything in this process touches the GPU.
     if "WORLD_SIZE" not in os.environ:
@@ -569,6 +636,9 @@ def main(rank_body=None, script=None, argv=None, child_argv=None):
                                                           broadcast_buffers=False, gradient_as_bucket_view=True)
     fused = use_graph and not a.torch_adam           # FlatAdam re-homes parameters/gradients/moments into flat buffers
     opt = make_optimizer(model, lr=VOX1["train_params"]["lr"], capturable=use_graph, fused=fused, clip=VOX1["train_params"]["clip"])
+    # --dump-outputs: the initial training state, identical in every run (seeded weights, fresh optimizer), for the last timed step to start
+    # from.  After any step the state carries the run-to-run spread of the float atomics, which every further Adam step amplifies
+    initial = [(t, t.detach().clone()) for t in training_state(model, opt)] if a.dump_outputs else None
     B = a.batch
     clip = VOX1["train_params"]["clip"]
     # synthetic pairs, different per rank (weak scaling: per-GPU work fixed), resident in HBM before timing
@@ -656,16 +726,26 @@ def main(rank_body=None, script=None, argv=None, child_argv=None):
     if launch == "eager" and not a.no_roofline:
         Ctx.profile = []
     t0 = time.perf_counter()
-    for _ in range(a.steps):
+    for _ in range(a.steps - (1 if initial else 0)):
         loss = step()
     barrier()
     dt = time.perf_counter() - t0
+    if initial:                                   # the last timed step from the initial state, restored outside the timed window
+        restore_state(model, opt, initial)
+        barrier()
+        t0 = time.perf_counter()
+        loss = step()
+        barrier()
+        dt += time.perf_counter() - t0
+        initial = None
     prof, Ctx.profile = Ctx.profile, None
     loss_val = float(loss.item())
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
     if world > 1:
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
     dt = float(tmax.item())
+    if a.dump_outputs and rank == 0:              # before anything below steps again
+        dump_outputs(a.dump_outputs, step_outputs(model, loss, gstep.gen if launch == "hipGraph" else None))
     nprof = a.steps
     if launch == "hipGraph" and not a.no_roofline and rank == 0:
         # roofline of the dominant kernel: the SAME step launched eagerly on the same stream with a HIP event pair

@@ -11,11 +11,11 @@ python -m pytest tests -m gpu -q > $O/gputest.log 2>&1; grep -E "passed|failed" 
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -2 $O/smoke.log
 fi
 if has bench; then
-S0=$SECONDS; python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default.log 2>$O/bench_default.err; echo "python bench.py --gpus 1 --steps 20 --warmup 5: $((SECONDS - S0)) s of wall time" > $O/bench_default.time
-python bench.py --steps 10 --warmup 3 --prior fomm --no-cpu-baseline > $O/bench_fomm.log 2>/dev/null
-python bench.py --steps 10 --warmup 3 --loss reference --no-cpu-baseline --no-forward > $O/bench_refloss.log 2>/dev/null
-python bench.py --steps 10 --warmup 3 --background --mfma bf16 --batch 16 --no-cpu-baseline --no-forward > $O/bench_config4.log 2>/dev/null
-python bench.py --size 512 --batch 4 --inference --steps 20 --warmup 3 > $O/bench_config5.log 2>/dev/null
+S0=$SECONDS; python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_default.log 2>$O/bench_default.err; echo "python bench.py --gpus 1 --steps 20 --warmup 5 --full: $((SECONDS - S0)) s of wall time" > $O/bench_default.time
+python bench.py --steps 10 --warmup 3 --prior fomm --no-cpu-baseline --full > $O/bench_fomm.log 2>/dev/null
+python bench.py --steps 10 --warmup 3 --loss reference --no-cpu-baseline --no-forward --full > $O/bench_refloss.log 2>/dev/null
+python bench.py --steps 10 --warmup 3 --background --mfma bf16 --batch 16 --no-cpu-baseline --no-forward --full > $O/bench_config4.log 2>/dev/null
+python bench.py --size 512 --batch 4 --inference --steps 20 --warmup 3 --full > $O/bench_config5.log 2>/dev/null
 MRFA_SYNCBN_GRAPH=1 MRFA_SYNCBN_FORCE_COLLECTIVE=1 python bench.py --sync-bn --force-exchange --steps 5 --warmup 2 --no-cpu-baseline --no-forward --no-roofline > $O/bench_syncbn_graph_one_rank.log 2>$O/bench_syncbn_graph_one_rank.err
 python bench.py --force-exchange --steps 5 --warmup 2 --no-cpu-baseline --no-forward --no-roofline > $O/bench_force_exchange_one_rank.log 2>/dev/null
 for f in default fomm refloss config4 config5 syncbn_graph_one_rank force_exchange_one_rank; do tail -1 $O/bench_$f.log | cut -c1-220; done
