@@ -287,8 +287,6 @@ __global__ __launch_bounds__(NT) void att_bwd_kv_mfma(const float* __restrict__ 
     }
 }
 
-int g_att_mfma = -1;
-
 template <typename K>
 int raise_lds(K kernel, size_t lds) {
     if (lds <= 64 * 1024) return 0;
@@ -297,13 +295,6 @@ int raise_lds(K kernel, size_t lds) {
 
 }  // namespace
 
-int mrfa_tuning_attention_mfma(int set) {
-    if (g_att_mfma < 0) { const char* e = getenv("MRFA_ATTENTION_MFMA"); g_att_mfma = !(e && e[0] == '0'); }
-    const int prev = g_att_mfma;
-    if (set >= 0) g_att_mfma = set != 0;
-    return prev;
-}
-
 // the MFMA kernels take the call: float4 accesses on every operand (16-byte aligned views, leading dimensions % 4 == 0) and the other side's operands of a
 // head -- tokens padded to a multiple of 16, + 16 floats, + 2 np floats in the key-side backward (dout != NULL) -- within the 160 KB of LDS.  Longer token
 // lists stay on the VALU kernels of tokenpose.hip, whose LDS image is smaller (no padding): a call they can serve never fails here
@@ -311,7 +302,7 @@ bool mrfa_attention_mfma_ok(int d, int n, const void* qkv, int ld, const void* o
     auto ok = [](const void* p, int l) { return p == nullptr || (aligned16(p) && (l % 4) == 0); };
     const size_t np = (size_t)(n + 15) / 16 * 16;
     const size_t lds = (2 * np * (d + 4) + 16 + (dout ? 2 * np : 0)) * sizeof(float);
-    return mrfa_tuning_attention_mfma(-1) && (d == 16 || d == 24 || d == 32) && lds <= 160 * 1024 && ok(qkv, ld) && ok(out, ldo) && ok(dout, lddo) &&
+    return g_tune.attention_mfma && (d == 16 || d == 24 || d == 32) && lds <= 160 * 1024 && ok(qkv, ld) && ok(out, ldo) && ok(dout, lddo) &&
            ok(dqkv, lddq);
 }
 

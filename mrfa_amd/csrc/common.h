@@ -10,12 +10,56 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 void mrfa_set_error(const char* fmt, ...);
 
+// conv_plan.hip: the dispatch switches, one table (mrfa_set_tuning keys; the MRFA_* environment variables seed them once, at load)
+struct MrfaTuning {
+    int conv_small_env;                    // MRFA_CONV_SMALL (no key: conv_small below is the runtime switch, both must be on)
+    int conv_small;
+    int conv_halo, conv_halo_min_tiles, conv_halo_pr, conv_halo_phase, conv_halo_bn256, conv_halo_bn192, conv_halo_bn64_fill;
+    int conv_lean, conv_lean_min_wgs, conv_lean_geo, gemm_lean;
+    int wgrad_halo, wgrad_halo_min_wgs, wgrad_halo_target_wgs, wgrad_halo_phase, wgrad_lean;
+    int conv_fewout3, attention_mfma, split_target_256;
+};
+extern MrfaTuning g_tune;
+
+// conv_halo.hip: patch geometry of the patch-tiled kernel (PR output rows per patch, BN output channels per workgroup, phase form of a fused upsample)
+struct HaloGeo { int PR, BN; bool phase; };
+
+// The launch plan of one mrfa_conv2d_nhwc call (conv_plan.hip): the kernel family and its geometry, decided once; the dispatcher launches it and the
+// capability queries read it.  Pure host arithmetic on the parameter block: no HIP call, no pointer dereferenced, no global written.
+enum class ConvFamily { lean, gemm_lean, small, halo, halo_dgrad, rows_split, rows_f32, refused };
+struct ConvPlan {
+    ConvFamily family;
+    char error[256];                       // refused: what mrfa_last_error() reports
+    long long M;                           // output rows N Hout Wout
+    int KT;                                // k-tiles of the row-tiled kernels
+    int lean_geo, gemm_cfg, small_tm, small_tn;       // conv_lean.hip geometry / gemm_lean configuration / conv_small.hip wave tile (x 16 rows, columns)
+    HaloGeo halo;
+    int BM, BN, splitk;                    // row-tiled tile and K split
+    bool w8;                               // 8-wave 128 x 128 fp32 tile
+    bool fused;                            // a K split finished by the tile's last workgroup (sk_ticket)
+    bool fin_in_launch;                    // fin_*: the launch's last workgroup finalizes the BatchNorm
+    bool reads_w;                          // the kernel reads the fp32 weight layout `w`
+    int last_config;                       // mrfa_conv2d_last_config()
+    // the answers of the capability queries for this block
+    bool groups_ok, bst_ok, stride2_ok, mask_ok, phase_dgrad_ok;
+};
+ConvPlan plan_conv(const mrfa_conv_params& p);
+
+enum class WgradFamily { lean, small, halo, tiled, refused };
+struct WgradPlan {
+    WgradFamily family;
+    char error[192];
+    long long M;
+    bool lean, small;                      // the kernels of wgrad_lean.hip / wgrad_small.hip take the problem
+    bool groups_ok, stride2_ok;
+};
+WgradPlan plan_wgrad(const mrfa_wgrad_params& p);
+
 // conv_split.hip: the 128 x 128 chunked implicit-GEMM tile on the bf16 matrix pipe with exactly split fp32 operands
 int mrfa_conv_split_launch(hipStream_t st, const mrfa_conv_params& p, int KT, long long M, int splitk, int BN);
 // conv_halo.hip: 3x3 stride-1 convolutions tiled over 2-D output patches, the input halo split once per channel chunk (same arithmetic)
-bool mrfa_conv_halo_eligible(const mrfa_conv_params& p);
-int mrfa_conv_halo_launch(hipStream_t st, const mrfa_conv_params& p);
-int mrfa_tuning_conv_small();      // mrfa_set_tuning("conv_small", 0 / 1)
+bool mrfa_conv_halo_eligible(const mrfa_conv_params& p, HaloGeo* geo);
+int mrfa_conv_halo_launch(hipStream_t st, const mrfa_conv_params& p, const HaloGeo& geo);
 // wgrad_split.hip: the 128 x 128 chunked, row-aligned weight-gradient tile in the same arithmetic
 int mrfa_wgrad_split_launch(hipStream_t st, const mrfa_wgrad_params& p, dim3 grid, long long M, long long kps, int tiles_n, int nsplit, int inner,
                             int total_splits, int taps, long long partial_stride, int BM, int BN);
@@ -23,42 +67,31 @@ int mrfa_wgrad_split_launch(hipStream_t st, const mrfa_wgrad_params& p, dim3 gri
 // wgrad_halo.hip: weight gradient of the 3x3 stride-1 layers, all nine taps from one staging of X / dY (transposing LDS reads)
 bool mrfa_wgrad_halo_eligible(const mrfa_wgrad_params& p);
 int mrfa_wgrad_halo_launch(hipStream_t st, const mrfa_wgrad_params& p);
-int mrfa_tuning_wgrad_halo_min(int set);   // mrfa_set_tuning("wgrad_halo_min_wgs", n)
-int mrfa_tuning_wgrad_halo_target(int set);
-int mrfa_tuning_wgrad_halo_phase(int set);
-int mrfa_tuning_wgrad_halo(int set);       // mrfa_set_tuning("wgrad_halo", 0 / 1); set < 0: query
 
 // conv_fewout3.hip: 3x3 layers with 1 / 2 output channels, channels across the lanes (true: handled, *rc = status)
 bool mrfa_fewout3_wgrad(hipStream_t st, const float* x, int ldx, int N, int H, int W, int Cin, const float* dy, int lddy, int Cout, int R, int pad,
                         float* dw, float* dbias, int* rc);
-int mrfa_tuning_fewout3(int set);          // mrfa_set_tuning("conv_fewout3", 0 / 1)
 
 // conv_lean.hip: the keypoint encoder's small-channel 3x3 layers (<= 128 channels, ~1 GFLOP): four-wave patches, the halo of all input channels split once
 // into LDS, weight fragments straight from the pre-split planes in global memory, split-operand arithmetic
-bool mrfa_conv_lean_eligible(const mrfa_conv_params& p);
-int mrfa_conv_lean_launch(hipStream_t st, const mrfa_conv_params& p);
-int mrfa_tuning_conv_lean(int set);        // mrfa_set_tuning("conv_lean", 0 / 1); set < 0: query
-int mrfa_tuning_conv_lean_min(int set);    // mrfa_set_tuning("conv_lean_min_wgs", n)
-bool mrfa_gemm_lean_eligible(const mrfa_conv_params& p, long long M);      // 1x1 convolutions / linears: the K-pipelined kernel of conv_lean.hip
-int mrfa_gemm_lean_launch(hipStream_t st, const mrfa_conv_params& p, long long M);
-int mrfa_tuning_gemm_lean(int set);        // mrfa_set_tuning("gemm_lean", 0 / 1); set < 0: query
-int mrfa_tuning_conv_lean_geo(int set);    // mrfa_set_tuning("conv_lean_geo", i): only geometry i of conv_lean.hip's table (-1: by workgroup count)
+int mrfa_conv_lean_pick(const mrfa_conv_params& p);                         // the geometry that runs the shape, -1: none
+int mrfa_conv_lean_launch(hipStream_t st, const mrfa_conv_params& p, int geo);
+int mrfa_gemm_lean_pick(const mrfa_conv_params& p, long long M);           // 1x1 convolutions / linears: the configuration of gemm_lean_kernel, -1: none
+int mrfa_gemm_lean_launch(hipStream_t st, const mrfa_conv_params& p, long long M, int cfg);
 
 // conv_small.hip: one wave per 16..32-row output tile, operands straight from L1/L2 into v_mfma_f32_16x16x4_f32 (small problems)
 bool mrfa_conv_small_eligible(const mrfa_conv_params& p, long long M);
-int mrfa_conv_small_launch(hipStream_t st, const mrfa_conv_params& p, long long M);
+int mrfa_conv_small_launch(hipStream_t st, const mrfa_conv_params& p, long long M, int tm, int tn);
 
 // attention_mfma.hip: multi-head attention forward / backward on v_mfma_f32_16x16x4_f32 (the VALU kernels of tokenpose.hip are the fallback)
 bool mrfa_attention_mfma_ok(int d, int n, const void* qkv, int ld, const void* out, int ldo, const void* dout, int lddo, const void* dqkv, int lddq);
 int mrfa_attention_fwd_mfma(hipStream_t st, const float* qkv, int ld, int B, int n, int heads, int d, float scale, float* out, int ldo, float* lse);
 int mrfa_attention_bwd_mfma(hipStream_t st, const float* qkv, int ld, const float* out, int ldo, const float* dout, int lddo, const float* lse,
                             float* delta, int B, int n, int heads, int d, float scale, float* dqkv, int lddq);
-int mrfa_tuning_attention_mfma(int set);   // mrfa_set_tuning("attention_mfma", 0 / 1); set < 0: query
 
 // wgrad_lean.hip: all nine taps of the keypoint encoder's <= 128-channel 3x3 layers per staging, many problems per launch, prologue per statistic group
 bool mrfa_wgrad_lean_eligible(const mrfa_wgrad_params& p);
 int mrfa_wgrad_lean_multi(hipStream_t st, const mrfa_wgrad_params* ps, int n, unsigned char* taken);      // launches the eligible ones, taken[i] = 1 for each
-int mrfa_tuning_wgrad_lean(int set);       // mrfa_set_tuning("wgrad_lean", 0 / 1); set < 0: query
 
 // wgrad_small.hip: one wave per 32 x 32 weight block of one tap over a pixel range (small problems)
 bool mrfa_wgrad_small_eligible(const mrfa_wgrad_params& p, long long M);

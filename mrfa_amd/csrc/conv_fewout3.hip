@@ -188,10 +188,8 @@ __global__ __launch_bounds__(256) void fewout3_wgrad_kernel(const float* __restr
     if (dbias && threadIdx.x < COUT) atomicAdd(dbias + threadIdx.x, red[COUT * 9 * Cin + threadIdx.x]);
 }
 
-int g_fewout3_on = 1;
-
 bool eligible(const float* x, int ldx, int Cin, int Cout, int R, int pad, int W) {
-    return g_fewout3_on && R == 3 && pad == 1 && (Cout == 1 || Cout == 2) && (Cin == 64 || Cin == 128 || Cin == 256) && (ldx % 4) == 0 &&
+    return g_tune.conv_fewout3 && R == 3 && pad == 1 && (Cout == 1 || Cout == 2) && (Cin == 64 || Cin == 128 || Cin == 256) && (ldx % 4) == 0 &&
            aligned16(x) && W >= 4;
 }
 
@@ -203,12 +201,6 @@ long long grid_for(long long units, int lpp) {
 }
 
 }  // namespace
-
-int mrfa_tuning_fewout3(int set) {
-    const int prev = g_fewout3_on;
-    if (set >= 0) g_fewout3_on = set != 0;
-    return prev;
-}
 
 #define FEW3R(KERNEL, RD, ...)                                                                                          \
     do {                                                                                                                \
@@ -269,5 +261,5 @@ extern "C" int mrfa_conv_fewout_dgrad(void* stream, const float* dy, int lddy, i
 }
 
 extern "C" int mrfa_conv_fewout_dgrad_supported(int Cin, int Cout, int R, int pad, int W, int lddx) {
-    return g_fewout3_on && R == 3 && pad == 1 && (Cout == 1 || Cout == 2) && (Cin == 64 || Cin == 128 || Cin == 256) && (lddx % 4) == 0 && W >= 4;
+    return g_tune.conv_fewout3 && R == 3 && pad == 1 && (Cout == 1 || Cout == 2) && (Cin == 64 || Cin == 128 || Cin == 256) && (lddx % 4) == 0 && W >= 4;
 }

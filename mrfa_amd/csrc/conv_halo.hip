@@ -446,48 +446,37 @@ __global__ __launch_bounds__(PR * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     if (p.fin_scale) fused_bn_finalize(p, (unsigned)total_tiles * gridDim.y, lin + total_tiles * (int)blockIdx.y, reinterpret_cast<double*>(smem), (int)(sizeof(smem) / 8));      // (every workgroup with a tile reaches this point with all of its threads)
 }
 
-int g_halo_on = -1;              // -1: not initialised (MRFA_CONV_HALO)
-int g_halo_min_tiles = 128;       // see halo_enough()
-int g_halo_pr = 0;               // 0 = by workgroup count, 4 / 8 = forced patch height
-int g_conv_small = 1;
-
-int g_halo_bn256 = 1;
-int g_halo_bn192 = 1;
-int g_halo_bn64_fill = 1;
-
-// (patch rows, BN): PR = 8 (8 waves, 1 workgroup / CU) when that still gives every CU a workgroup, else PR = 4 (4 waves, 2 workgroups
-// per CU); BN = 256 (each wave 64 pixels x 128 channels: the halo is staged once for twice the MFMAs, 18 instead of 24 fragment reads
-// per 48 MFMAs) when Cout pads to a multiple of 256 anyway and the workgroup count allows
-int g_halo_phase = 1;
-
 // the phase form of a fused upsample applies: pre-summed phase weights present, the LOW-resolution grid tiles into 8 x 32 patches
 bool halo_phase(const mrfa_conv_params& p) {
     const int mode = mrfa_get_mfma_mode();
-    return (mode == 1 || mode == 2) && g_halo_phase && p.ups == 1 && p.w_phase != nullptr && (p.Win % PW) == 0 && (p.Hin % 8) == 0 && 3 * p.w_phase_piece < (1ll << 31);
+    return (mode == 1 || mode == 2) && g_tune.conv_halo_phase && p.ups == 1 && p.w_phase != nullptr && (p.Win % PW) == 0 && (p.Hin % 8) == 0 && 3 * p.w_phase_piece < (1ll << 31);
 }
 
-// enough workgroups for a launch with `tiles` workgroups of width bn?  One per CU (2 x g_halo_min_tiles = 256) in general; half a chip's worth is
+// enough workgroups for a launch with `tiles` workgroups of width bn?  One per CU (2 x conv_halo_min_tiles = 256) in general; half a chip's worth is
 // still better than the row-tiled kernel for <= 128-wide tiles on >= 64-pixel-wide outputs with >= 64 channels on both sides (measured: 256->128
 // @64^2 forward 174 -> 148 us, 192->128 152 -> 115, the dense-motion up block 512->128 @32->64 in phase form 284 -> 145; but 512->512 @32^2
 // 259 -> 285 and 32->32 @64^2 15 -> 23 us)
 bool halo_enough(const mrfa_conv_params& p, long long tiles, int bn) {
-    if (tiles >= 2ll * g_halo_min_tiles) return true;
-    return bn <= 128 && tiles >= g_halo_min_tiles && p.Wout >= 64 && p.Cin >= 64 && p.Cout >= 64;
+    if (tiles >= 2ll * g_tune.conv_halo_min_tiles) return true;
+    return bn <= 128 && tiles >= g_tune.conv_halo_min_tiles && p.Wout >= 64 && p.Cin >= 64 && p.Cout >= 64;
 }
 
+// (patch rows, BN): PR = 8 (8 waves, 1 workgroup / CU) when that still gives every CU a workgroup, else PR = 4 (4 waves, 2 workgroups
+// per CU); BN = 256 (each wave 64 pixels x 128 channels: the halo is staged once for twice the MFMAs, 18 instead of 24 fragment reads
+// per 48 MFMAs) when Cout pads to a multiple of 256 anyway and the workgroup count allows
 void halo_config(const mrfa_conv_params& p, int& PR, int& BN) {
     PR = 0;
     BN = p.Cout <= 64 ? 64 : 128;
-    const bool wide = g_halo_bn256 && p.Cout > 128 && cdiv(p.Cout, 256) * 256 == cdiv(p.Cout, 128) * 128;
+    const bool wide = g_tune.conv_halo_bn256 && p.Cout > 128 && cdiv(p.Cout, 256) * 256 == cdiv(p.Cout, 128) * 128;
     if (halo_phase(p)) {                           // four phase workgroups per low-resolution patch
         const long long patches = (long long)p.N * (p.Hin / 8) * (p.Win / PW) * 4;
         if (wide && halo_enough(p, patches * cdiv(p.Cout, 256), 256)) { PR = 8; BN = 256; return; }
         if (halo_enough(p, patches * cdiv(p.Cout, BN), BN)) { PR = 8; return; }
     }
     const long long patches8 = (long long)p.N * cdiv(p.Hout, 8) * (p.Wout / PW), patches4 = (long long)p.N * cdiv(p.Hout, 4) * (p.Wout / PW);
-    if (g_halo_pr != 4 && p.Hout % 8 == 0) {
+    if (g_tune.conv_halo_pr != 4 && p.Hout % 8 == 0) {
         // 192-wide tiles where they pad less than 128- / 256-wide ones (data gradients into 160 / 192 channels: 256 -> 192 columns of MFMA work)
-        if (g_halo_bn192 && !p.in_scale && cdiv(p.Cout, 192) * 192 < cdiv(p.Cout, 128) * 128 && halo_enough(p, patches8 * cdiv(p.Cout, 192), 192)) {
+        if (g_tune.conv_halo_bn192 && !p.in_scale && cdiv(p.Cout, 192) * 192 < cdiv(p.Cout, 128) * 128 && halo_enough(p, patches8 * cdiv(p.Cout, 192), 192)) {
             PR = 8;
             BN = 192;
             return;
@@ -495,8 +484,8 @@ void halo_config(const mrfa_conv_params& p, int& PR, int& BN) {
         if (wide && halo_enough(p, patches8 * cdiv(p.Cout, 256), 256)) { PR = 8; BN = 256; return; }
         // too few 128-wide tiles for one workgroup per CU but enough 64-wide ones: fill the chip with the narrower tile (more fragment reads per
         // MFMA, twice the workgroups) -- the low-resolution levels (512 -> 512 @32^2, 256 -> 128 @64^2)
-        if (g_halo_bn64_fill && BN == 128 && patches8 * cdiv(p.Cout, 128) < 2ll * g_halo_min_tiles &&
-            patches8 * cdiv(p.Cout, 64) >= 2ll * g_halo_min_tiles) {
+        if (g_tune.conv_halo_bn64_fill && BN == 128 && patches8 * cdiv(p.Cout, 128) < 2ll * g_tune.conv_halo_min_tiles &&
+            patches8 * cdiv(p.Cout, 64) >= 2ll * g_tune.conv_halo_min_tiles) {
             PR = 8;
             BN = 64;
             return;
@@ -505,7 +494,7 @@ void halo_config(const mrfa_conv_params& p, int& PR, int& BN) {
     }
     // 4-row patches run two workgroups per CU: they need twice the workgroups to fill the chip (measured: 512->512 @32^2, 256 workgroups of
     // 4 rows lose to the row-tiled kernel with its K split)
-    if (g_halo_pr != 8 && patches4 * cdiv(p.Cout, BN) >= 4ll * g_halo_min_tiles) PR = 4;
+    if (g_tune.conv_halo_pr != 8 && patches4 * cdiv(p.Cout, BN) >= 4ll * g_tune.conv_halo_min_tiles) PR = 4;
 }
 
 // (is the launch the phase form?  halo_config picks it first; it falls through to the plain form when the phase grid is too small)
@@ -517,41 +506,10 @@ bool halo_uses_phase(const mrfa_conv_params& p, int PR, int BN) {
 
 }  // namespace
 
-static bool halo_on() {
-    if (g_halo_on < 0) { const char* e = getenv("MRFA_CONV_HALO"); g_halo_on = !(e && e[0] == '0'); }
-    return g_halo_on != 0;
-}
-
-extern "C" int mrfa_set_tuning(const char* key, int value) {
-    if (!key) return -1;
-    if (!strcmp(key, "conv_halo")) { const int prev = halo_on(); g_halo_on = value != 0; return prev; }
-    if (!strcmp(key, "conv_halo_min_tiles")) { const int prev = g_halo_min_tiles; g_halo_min_tiles = value; return prev; }
-    if (!strcmp(key, "conv_halo_phase")) { const int prev = g_halo_phase; g_halo_phase = value != 0; return prev; }
-    if (!strcmp(key, "conv_halo_bn256")) { const int prev = g_halo_bn256; g_halo_bn256 = value != 0; return prev; }
-    if (!strcmp(key, "conv_halo_bn64_fill")) { const int prev = g_halo_bn64_fill; g_halo_bn64_fill = value != 0; return prev; }
-    if (!strcmp(key, "conv_halo_bn192")) { const int prev = g_halo_bn192; g_halo_bn192 = value != 0; return prev; }
-    if (!strcmp(key, "conv_halo_pr")) { const int prev = g_halo_pr; g_halo_pr = value; return prev; }
-    if (!strcmp(key, "wgrad_halo")) return mrfa_tuning_wgrad_halo(value != 0);
-    if (!strcmp(key, "wgrad_halo_min_wgs")) return mrfa_tuning_wgrad_halo_min(value);
-    if (!strcmp(key, "wgrad_halo_target_wgs")) return mrfa_tuning_wgrad_halo_target(value);
-    if (!strcmp(key, "wgrad_halo_phase")) return mrfa_tuning_wgrad_halo_phase(value);
-    if (!strcmp(key, "conv_fewout3")) return mrfa_tuning_fewout3(value != 0);
-    if (!strcmp(key, "attention_mfma")) return mrfa_tuning_attention_mfma(value != 0);
-    if (!strcmp(key, "conv_small")) { const int prev = g_conv_small; g_conv_small = value != 0; return prev; }
-    if (!strcmp(key, "conv_lean")) return mrfa_tuning_conv_lean(value != 0);
-    if (!strcmp(key, "conv_lean_min_wgs")) return mrfa_tuning_conv_lean_min(value);
-    if (!strcmp(key, "conv_lean_geo")) return mrfa_tuning_conv_lean_geo(value);
-    if (!strcmp(key, "wgrad_lean")) return mrfa_tuning_wgrad_lean(value != 0);
-    if (!strcmp(key, "gemm_lean")) return mrfa_tuning_gemm_lean(value);
-    return -1;
-}
-
-int mrfa_tuning_conv_small() { return g_conv_small; }
-
 // ups == 2: phase DATA GRADIENT of a fused-upsample 3x3 layer (x = high-resolution gradient, y = low-resolution input gradient)
 static bool halo_phase_dgrad(const mrfa_conv_params& p) {
     const int mode = mrfa_get_mfma_mode();
-    if (!halo_on() || !g_halo_phase || (mode != 1 && mode != 2)) return false;
+    if (!g_tune.conv_halo || !g_tune.conv_halo_phase || (mode != 1 && mode != 2)) return false;
     if (p.ups != 2 || !p.w_phase || p.kflat > 0 || p.R != 3 || p.S != 3 || p.pad != 1 || p.nbatch > 1 || p.splitk > 1 || p.tile || p.in_scale) return false;
     if (p.Hin != 2 * p.Hout || p.Win != 2 * p.Wout || (p.Wout % PW) != 0 || (p.Hout % 8) != 0 || (p.Cin % 32) != 0 || p.Cout < 32) return false;
     if ((p.ldy % 4) != 0 || !aligned16(p.y) || (p.ldx % 4) != 0 || !aligned16(p.x) || 3 * p.w_phase_piece >= (1ll << 31) || p.w_tap >= (1ll << 31)) return false;
@@ -559,14 +517,14 @@ static bool halo_phase_dgrad(const mrfa_conv_params& p) {
     return true;
 }
 
-extern "C" int mrfa_conv2d_phase_dgrad_supported(const mrfa_conv_params* p) { return p && halo_phase_dgrad(*p) ? 1 : 0; }
-
-extern "C" int mrfa_conv2d_mask_supported(const mrfa_conv_params* p) { return p && p->kflat == 0 && mrfa_conv_halo_eligible(*p) ? 1 : 0; }
-
-bool mrfa_conv_halo_eligible(const mrfa_conv_params& p) {
-    if (p.ups == 2) return halo_phase_dgrad(p);
+// 1: the shape runs here; *geo = its patch geometry
+bool mrfa_conv_halo_eligible(const mrfa_conv_params& p, HaloGeo* geo) {
+    if (p.ups == 2) {                                // phase data gradient: 8-row patches on the output grid, <= 128-wide tiles
+        *geo = {8, p.Cout <= 64 ? 64 : 128, false};
+        return halo_phase_dgrad(p);
+    }
     const int mode = mrfa_get_mfma_mode();
-    if (!halo_on() || (mode != 1 && mode != 2 && mode != 3)) return false;       // (mode 3: w_split = ONE plane rounded to nearest even, pack modes 14 / 15)
+    if (!g_tune.conv_halo || (mode != 1 && mode != 2 && mode != 3)) return false;       // (mode 3: w_split = ONE plane rounded to nearest even, pack modes 14 / 15)
     if (p.kflat > 0 || p.R != 3 || p.S != 3 || p.pad != 1 || !p.w_split || p.nbatch > 1 || p.splitk > 1 || p.tile || p.stride > 1 || p.stride < 0) return false;
     if ((p.Wout % PW) != 0 || p.Hout < 4 || (p.Cin % 32) != 0 || p.Cout < 32) return false;
     if (p.Hout != (p.Hin << p.ups) || p.Wout != (p.Win << p.ups)) return false;
@@ -576,18 +534,13 @@ bool mrfa_conv_halo_eligible(const mrfa_conv_params& p) {
     if (p.in_scale && !p.in_relu) return false;
     int PR, BN;
     halo_config(p, PR, BN);
+    *geo = {PR, BN, halo_uses_phase(p, PR, BN)};
     return PR != 0;
 }
 
-int mrfa_conv_halo_launch(hipStream_t st, const mrfa_conv_params& p) {
-    int PR, BN;
-    if (p.ups == 2) {                                // phase data gradient: 8-row patches on the output grid, <= 128-wide tiles
-        PR = 8;
-        BN = p.Cout <= 64 ? 64 : 128;
-    } else {
-        halo_config(p, PR, BN);
-    }
-    const bool phase = p.ups != 2 && halo_uses_phase(p, PR, BN);
+int mrfa_conv_halo_launch(hipStream_t st, const mrfa_conv_params& p, const HaloGeo& geo) {
+    const int PR = geo.PR, BN = geo.BN;
+    const bool phase = geo.phase;
     const int tiles_n = cdiv(p.Cout, BN), tiles_x = (phase ? p.Win : p.Wout) / PW, tiles_y = cdiv(phase ? p.Hin : p.Hout, PR);
     const long long total = (long long)p.N * tiles_y * tiles_x * tiles_n;
     dim3 grid((unsigned)(cdiv(total, 8) * 8), phase ? 4u : 1u);

@@ -591,14 +591,10 @@ __global__ __launch_bounds__(256, 2) void gemm_lean_kernel(const mrfa_conv_param
     lean_finish<MT, 1, WCO, KS>(p, acc, smem, (int)((size_t)2 * STAGE / 8), wave, lane, tid, wk, wg_on, n0, cb, fhalf, e_row, e_ok, grp, pre_res, pre_bx);
 }
 
-int g_lean_on = -1;              // -1: not initialised (MRFA_CONV_LEAN)
-int g_lean_min_wgs = 128;
-int g_lean_geo = -1;             // >= 0: only this entry of LEAN_CFGS (tests)
-
 struct LeanCfg { int TW, WPX, WCO, KS, MT, NSC; };
 
 // the instantiated geometries, in order of preference (fewest halo re-reads first); a geometry applies when Cin = 16 KS NSC, the output tiles into
-// its patches and the launch has at least g_lean_min_wgs workgroups
+// its patches and the launch has at least conv_lean_min_wgs workgroups
 constexpr LeanCfg LEAN_CFGS[] = {
     // two pixel tiles per wave: a weight fragment (16 bytes per lane from L1) feeds twelve MFMAs -- with one tile per wave the four SIMDs of a CU ask
     // the L1 for 3 KB per 192 matrix cycles each = its whole 64 bytes per clock
@@ -623,18 +619,13 @@ long long lean_wgs(const mrfa_conv_params& p, const LeanCfg& c) {
 int lean_pick(const mrfa_conv_params& p) {
     for (int i = 0; i < N_LEAN_CFGS; ++i) {
         const LeanCfg& c = LEAN_CFGS[i];
-        if (g_lean_geo >= 0 && i != g_lean_geo) continue;
+        if (g_tune.conv_lean_geo >= 0 && i != g_tune.conv_lean_geo) continue;
         if (p.Cin != 16 * c.KS * c.NSC || (p.Wout % c.TW) != 0) continue;
         // two-tile geometries run one workgroup per CU: they need twice the workgroups
-        if (g_lean_geo < 0 && lean_wgs(p, c) < (long long)g_lean_min_wgs * c.MT) continue;
+        if (g_tune.conv_lean_geo < 0 && lean_wgs(p, c) < (long long)g_tune.conv_lean_min_wgs * c.MT) continue;
         return i;
     }
     return -1;
-}
-
-bool lean_on() {
-    if (g_lean_on < 0) { const char* e = getenv("MRFA_CONV_LEAN"); g_lean_on = !(e && e[0] == '0'); }
-    return g_lean_on != 0;
 }
 
 template <int I, bool PRO, int NP>
@@ -665,52 +656,31 @@ int lean_launch_i(hipStream_t st, const mrfa_conv_params& p, int mode) {
 
 }  // namespace
 
-int mrfa_tuning_conv_lean(int set) {
-    const int prev = lean_on();
-    if (set >= 0) g_lean_on = set != 0;
-    return prev;
-}
-int mrfa_tuning_conv_lean_geo(int set) {
-    const int prev = g_lean_geo;
-    g_lean_geo = set;
-    return prev;
-}
-int mrfa_tuning_conv_lean_min(int set) {
-    const int prev = g_lean_min_wgs;
-    if (set >= 0) g_lean_min_wgs = set;
-    return prev;
-}
-
-// 1: the shape runs here.  3x3 / pad 1 / stride 1 in a split-operand (or plain bf16) mode with pre-split weights, 16-byte addressable tensors,
-// whole channel quads, one of the instantiated geometries, and a problem small enough that conv_halo.hip's 8-row patches cannot fill the chip
-bool mrfa_conv_lean_eligible(const mrfa_conv_params& p) {
+// the geometry that runs the shape here (-1: none).  3x3 / pad 1 / stride 1 in a split-operand (or plain bf16) mode with pre-split weights, 16-byte
+// addressable tensors, whole channel quads, one of the instantiated geometries, and a problem small enough that conv_halo.hip's 8-row patches cannot fill the chip
+int mrfa_conv_lean_pick(const mrfa_conv_params& p) {
     const int mode = mrfa_get_mfma_mode();
-    if (!lean_on() || (mode != 1 && mode != 2 && mode != 3)) return false;
-    if (p.kflat > 0 || p.R != 3 || p.S != 3 || p.pad != 1 || !p.w_split || p.nbatch > 1 || p.splitk > 1 || p.tile || p.stride > 1 || p.stride < 0 || p.ups || p.mask) return false;
-    if (mode != 3 && p.w_piece <= 0) return false;
-    if (p.Hout != p.Hin || p.Wout != p.Win) return false;
-    if ((p.Cout % 32) != 0 || p.Cout > 128 || (p.Cin % 32) != 0) return false;
-    if ((p.ldy % 4) != 0 || !aligned16(p.y) || (p.ldx % 4) != 0 || !aligned16(p.x)) return false;
-    if (p.res && ((p.ldr % 4) != 0 || !aligned16(p.res))) return false;
-    if (p.bias && !aligned16(p.bias)) return false;
-    if (p.out_scale && (!aligned16(p.out_scale) || !aligned16(p.out_shift))) return false;
-    if (p.in_scale && (!p.in_relu || !aligned16(p.in_scale) || !aligned16(p.in_shift))) return false;
+    if (!g_tune.conv_lean || (mode != 1 && mode != 2 && mode != 3)) return -1;
+    if (p.kflat > 0 || p.R != 3 || p.S != 3 || p.pad != 1 || !p.w_split || p.nbatch > 1 || p.splitk > 1 || p.tile || p.stride > 1 || p.stride < 0 || p.ups || p.mask) return -1;
+    if (mode != 3 && p.w_piece <= 0) return -1;
+    if (p.Hout != p.Hin || p.Wout != p.Win) return -1;
+    if ((p.Cout % 32) != 0 || p.Cout > 128 || (p.Cin % 32) != 0) return -1;
+    if ((p.ldy % 4) != 0 || !aligned16(p.y) || (p.ldx % 4) != 0 || !aligned16(p.x)) return -1;
+    if (p.res && ((p.ldr % 4) != 0 || !aligned16(p.res))) return -1;
+    if (p.bias && !aligned16(p.bias)) return -1;
+    if (p.out_scale && (!aligned16(p.out_scale) || !aligned16(p.out_shift))) return -1;
+    if (p.in_scale && (!p.in_relu || !aligned16(p.in_scale) || !aligned16(p.in_shift))) return -1;
     if (p.bst_x && ((p.bst_ldx % 4) != 0 || !aligned16(p.bst_x) || !aligned16(p.bst_scale) || !aligned16(p.bst_shift) || !aligned16(p.bst_mean) || !aligned16(p.bst_invstd)))
-        return false;
-    if (p.groups > 1 && (p.N % p.groups) != 0) return false;
-    if (3 * p.w_piece >= (1ll << 31) || 9 * p.w_tap >= (1ll << 31) || (long long)p.N * p.Hin * p.Win * p.ldx >= (1ll << 31)) return false;
+        return -1;
+    if (p.groups > 1 && (p.N % p.groups) != 0) return -1;
+    if (3 * p.w_piece >= (1ll << 31) || 9 * p.w_tap >= (1ll << 31) || (long long)p.N * p.Hin * p.Win * p.ldx >= (1ll << 31)) return -1;
     // ~2.5 GFLOP at most: beyond that the 8-row patches of conv_halo.hip (weights shared through LDS by 8 waves) are the faster kernel
-    if (2.0 * (double)p.N * p.Hout * p.Wout * p.Cout * 9.0 * p.Cin > 2.6e9) return false;
-    return lean_pick(p) >= 0;
+    if (2.0 * (double)p.N * p.Hout * p.Wout * p.Cout * 9.0 * p.Cin > 2.6e9) return -1;
+    return lean_pick(p);
 }
 
 // ---- 1x1 convolutions / linears on gemm_lean_kernel
 namespace {
-int g_gemm_lean_on = -1;
-bool gemm_lean_on() {
-    if (g_gemm_lean_on < 0) { const char* e = getenv("MRFA_GEMM_LEAN"); g_gemm_lean_on = e ? atoi(e) : 1; }      // 0 off, 1 where measured faster, 2 wherever it can run
-    return g_gemm_lean_on != 0;
-}
 // 0: 64 rows x 128 channels per workgroup; 1: 64 x 64 with the input channels in two slices (short N or long K: more workgroups, half the k-loop)
 int gemm_lean_cfg(const mrfa_conv_params& p, long long M) {
     const long long rows = (M + 63) / 64;
@@ -737,51 +707,45 @@ int gemm_lean_launch_cfg(hipStream_t st, const mrfa_conv_params& p, long long M,
 }
 }  // namespace
 
-int mrfa_tuning_gemm_lean(int set) {
-    gemm_lean_on();
-    const int prev = g_gemm_lean_on;
-    if (set >= 0) g_gemm_lean_on = set > 2 ? 2 : set;
-    return prev;
-}
-
-// 1: the 1x1 convolution / linear runs on gemm_lean_kernel: a split-operand (or plain bf16) mode with pre-split weights, 32-aligned channel counts, 16-byte
-// addressable tensors, no prologue, and a problem small enough that the 128-row tiles of conv_split.hip cannot fill the chip with long k-loops
-bool mrfa_gemm_lean_eligible(const mrfa_conv_params& p, long long M) {
+// the configuration of gemm_lean_kernel that runs the 1x1 convolution / linear (-1: none): a split-operand (or plain bf16) mode with pre-split weights,
+// 32-aligned channel counts, 16-byte addressable tensors, no prologue, and a problem small enough that the 128-row tiles of conv_split.hip cannot fill the
+// chip with long k-loops
+int mrfa_gemm_lean_pick(const mrfa_conv_params& p, long long M) {
     const int mode = mrfa_get_mfma_mode();
-    if (!gemm_lean_on() || (mode != 1 && mode != 2 && mode != 3)) return false;
-    if (p.kflat > 0 || p.R != 1 || p.S != 1 || p.pad != 0 || !p.w_split || p.nbatch > 1 || p.splitk > 1 || p.tile || p.stride > 1 || p.stride < 0 || p.ups || p.mask || p.in_scale) return false;
-    if (mode != 3 && p.w_piece <= 0) return false;
-    if (p.Hout != p.Hin || p.Wout != p.Win) return false;
-    if ((p.Cout % 32) != 0 || (p.Cin % 32) != 0 || p.Cin > 1024 || M < 256) return false;
-    if ((p.ldy % 4) != 0 || !aligned16(p.y) || (p.ldx % 4) != 0 || !aligned16(p.x)) return false;
-    if (p.res && ((p.ldr % 4) != 0 || !aligned16(p.res))) return false;
-    if (p.bias && !aligned16(p.bias)) return false;
-    if (p.out_scale && (!aligned16(p.out_scale) || !aligned16(p.out_shift))) return false;
+    if (!g_tune.gemm_lean || (mode != 1 && mode != 2 && mode != 3)) return -1;
+    if (p.kflat > 0 || p.R != 1 || p.S != 1 || p.pad != 0 || !p.w_split || p.nbatch > 1 || p.splitk > 1 || p.tile || p.stride > 1 || p.stride < 0 || p.ups || p.mask || p.in_scale) return -1;
+    if (mode != 3 && p.w_piece <= 0) return -1;
+    if (p.Hout != p.Hin || p.Wout != p.Win) return -1;
+    if ((p.Cout % 32) != 0 || (p.Cin % 32) != 0 || p.Cin > 1024 || M < 256) return -1;
+    if ((p.ldy % 4) != 0 || !aligned16(p.y) || (p.ldx % 4) != 0 || !aligned16(p.x)) return -1;
+    if (p.res && ((p.ldr % 4) != 0 || !aligned16(p.res))) return -1;
+    if (p.bias && !aligned16(p.bias)) return -1;
+    if (p.out_scale && (!aligned16(p.out_scale) || !aligned16(p.out_shift))) return -1;
     if (p.bst_x && ((p.bst_ldx % 4) != 0 || !aligned16(p.bst_x) || !aligned16(p.bst_scale) || !aligned16(p.bst_shift) || !aligned16(p.bst_mean) || !aligned16(p.bst_invstd)))
-        return false;
-    if (p.groups > 1 && ((p.N % p.groups) != 0 || ((M / p.groups) % 64) != 0)) return false;      // a workgroup's 64 rows inside one statistic group
-    if (3 * p.w_piece >= (1ll << 31) || M * p.ldx >= (1ll << 31) * 2) return false;
-    if (2.0 * (double)M * p.Cout * (double)p.Cin > 2.6e9) return false;
-    if (g_gemm_lean_on >= 2) return true;
+        return -1;
+    if (p.groups > 1 && ((p.N % p.groups) != 0 || ((M / p.groups) % 64) != 0)) return -1;      // a workgroup's 64 rows inside one statistic group
+    if (3 * p.w_piece >= (1ll << 31) || M * p.ldx >= (1ll << 31) * 2) return -1;
+    if (2.0 * (double)M * p.Cout * (double)p.Cin > 2.6e9) return -1;
+    const int cfg = gemm_lean_cfg(p, M);
+    if (g_tune.gemm_lean >= 2) return cfg;
     // measured (profiles/r6_gemm_lean_bench.txt): ahead on the transformer's token linears (4 416 rows, 192 / 576 channels: 17 against 25-27 us); behind the
     // 128-row tiles on the 65 536-row layer1 bottlenecks and behind conv_small's 32-row tiles where 64-row tiles leave most of the chip idle (the fuse layers)
-    const long long wgs = ((M + 63) / 64) * cdiv(p.Cout, gemm_lean_cfg(p, M) == 0 ? 128 : 64);
-    return wgs >= 192 && M <= 32768 && p.Cout >= 64;
+    const long long wgs = ((M + 63) / 64) * cdiv(p.Cout, cfg == 0 ? 128 : 64);
+    return wgs >= 192 && M <= 32768 && p.Cout >= 64 ? cfg : -1;
 }
 
-int mrfa_gemm_lean_launch(hipStream_t st, const mrfa_conv_params& p, long long M) {
+int mrfa_gemm_lean_launch(hipStream_t st, const mrfa_conv_params& p, long long M, int cfg) {
     const int mode = mrfa_get_mfma_mode();
-    const int rc = gemm_lean_cfg(p, M) == 0 ? gemm_lean_launch_cfg<4, 1>(st, p, M, mode) : gemm_lean_launch_cfg<2, 2>(st, p, M, mode);
+    const int rc = cfg == 0 ? gemm_lean_launch_cfg<4, 1>(st, p, M, mode) : gemm_lean_launch_cfg<2, 2>(st, p, M, mode);
     if (rc) return rc;
     MRFA_CHECK_LAUNCH("mrfa_conv2d_nhwc(gemm_lean)");
     return 0;
 }
 
-int mrfa_conv_lean_launch(hipStream_t st, const mrfa_conv_params& p) {
+int mrfa_conv_lean_launch(hipStream_t st, const mrfa_conv_params& p, int geo) {
     const int mode = mrfa_get_mfma_mode();
-    const int i = lean_pick(p);
     int rc = 0;
-    switch (i) {
+    switch (geo) {
         case 0: rc = lean_launch_i<0>(st, p, mode); break;
         case 1: rc = lean_launch_i<1>(st, p, mode); break;
         case 2: rc = lean_launch_i<2>(st, p, mode); break;

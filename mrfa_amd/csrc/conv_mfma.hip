@@ -369,7 +369,6 @@ int launch_cfg(hipStream_t st, const mrfa_conv_params& p, int KT, long long M, i
 // 2: the same kernels keeping the three leading products only (bf16x3: 2^-16-class product error instead of 2^-24);
 // 3: plain bf16 operands (round-to-nearest-even), one product: the arithmetic of a bf16 autocast (BASELINE config 4)
 static int g_mfma_mode = 0;
-static int g_split_target_256 = getenv("MRFA_SPLIT_TARGET_256") ? atoi(getenv("MRFA_SPLIT_TARGET_256")) : 1;
 extern "C" int mrfa_set_mfma_mode(int mode) {
     if (mode < 0 || mode > 3) { mrfa_set_error("set_mfma_mode: unknown mode %d", mode); return 1; }
     g_mfma_mode = mode;
@@ -381,219 +380,16 @@ static thread_local int g_last_tile = 0;
 // (BM << 16) | (BN << 4) | (flat << 1) | (splitk > 1) of the most recent mrfa_conv2d_nhwc launch on this thread
 extern "C" int mrfa_conv2d_last_config(void) { return g_last_tile; }
 
-extern "C" int mrfa_conv2d_stride_supported(const mrfa_conv_params* p) {
-    if (!p || p->stride != 2) return 0;
-    if (p->Hout != (p->Hin + 2 * p->pad - p->R) / 2 + 1 || p->Wout != (p->Win + 2 * p->pad - p->S) / 2 + 1) return 0;
-    if (p->kflat > 0) return (!p->ups && p->nbatch <= 1 && p->splitk <= 1 && p->ktab) ? 1 : 0;      // flat-K gather of the fp32 tile kernel
-    if (!mrfa_tuning_conv_small()) return 0;
-    static const bool small_on = [] { const char* e = getenv("MRFA_CONV_SMALL"); return !(e && e[0] == '0'); }();
-    return small_on && mrfa_conv_small_eligible(*p, (long long)p->N * p->Hout * p->Wout) ? 1 : 0;
-}
-
-static int conv2d_dispatch(void* stream, const mrfa_conv_params* pp, bool* fin_done, int* dry_split = nullptr, int* dry_reads_w = nullptr);
-
-extern "C" int mrfa_conv2d_bwdstats_supported(const mrfa_conv_params* p) {
-    if (!p || !p->stats || p->fin_scale || p->stride < 0 || p->kflat > 0) return 0;
-    if (mrfa_conv_lean_eligible(*p) || mrfa_gemm_lean_eligible(*p, (long long)p->N * p->Hout * p->Wout)) return 1;
-    static const bool small_on = [] { const char* e = getenv("MRFA_CONV_SMALL"); return !(e && e[0] == '0'); }();
-    return small_on && mrfa_tuning_conv_small() && mrfa_conv_small_eligible(*p, (long long)p->N * p->Hout * p->Wout) ? 1 : 0;
-}
-
-// statistic groups: every kernel's output tile is at most 128 rows (and divides 128), the patch-tiled kernel's lies inside one image; a K split sums
-// its partial tiles in a pass whose workgroups stride over ALL rows, so grouped launches never split K (the automatic choice is switched off for them)
-extern "C" int mrfa_conv2d_groups_supported(const mrfa_conv_params* p) {
-    if (!p || p->groups <= 1) return p ? 1 : 0;
-    if (!p->stats && !p->fin_scale && !p->bst_x && !p->in_scale) return 1;       // (nothing per group in this call)
-    if (p->nbatch > 1 || p->splitk > 1) return 0;
-    const long long M = (long long)p->N * p->Hout * p->Wout;
-    const long long rows = group_rows(*p, M);
-    if (rows <= 0) return 0;
-    if (p->kflat == 0 && mrfa_conv_lean_eligible(*p)) return 1;                                      // (a patch lies inside one image)
-    if (p->kflat == 0 && mrfa_gemm_lean_eligible(*p, M)) return 1;                                   // (its own rule: rows of a group % 64 == 0)
-    if (p->in_scale) return 0;                                                                       // (prologue vectors per group: conv_lean.hip only)
-    if ((rows % 128) == 0) return 1;
-    // shorter groups: the kernels whose tiles are smaller than 128 rows, where the dispatch would pick them
-    static const bool small_on = [] { const char* e = getenv("MRFA_CONV_SMALL"); return !(e && e[0] == '0'); }();
-    if (small_on && mrfa_tuning_conv_small() && mrfa_conv_small_eligible(*p, M)) return 1;       // (its own rule: rows % 64 == 0)
-    return p->kflat == 0 && p->stride <= 1 && mrfa_conv_halo_eligible(*p) ? 1 : 0;                // (a patch lies inside one image)
-}
-
-// v8: the K slices conv2d_dispatch would use for these parameters (the dispatch itself, stopped before its first launch)
-extern "C" int mrfa_conv2d_split_k(const mrfa_conv_params* p) {
-    if (!p) return 1;
-    if (p->splitk > 1) return p->splitk;
-    int k = 1;
-    bool fin_done = false;
-    return conv2d_dispatch(nullptr, p, &fin_done, &k) ? 1 : k;
-}
-
-// v9: does the kernel a call with these parameters would run read the fp32 weight layout `w` at all?  0: it reads the pre-split planes only (conv_halo.hip,
-// conv_lean.hip, the row-tiled split-operand tile with w_split in the split modes) -- the caller may pass any non-NULL `w` and need not keep (or refresh, once
-// per optimizer step) that layout: for the decoder's ~100 M parameters that is 8 of the 28 bytes per parameter the per-step re-packing moved.
-extern "C" int mrfa_conv2d_reads_fp32_weights(const mrfa_conv_params* p) {
-    if (!p || (!p->w_split && !p->w_phase)) return 1;
-    int k = 1, reads = 1;
-    bool fin_done = false;
-    return conv2d_dispatch(nullptr, p, &fin_done, &k, &reads) ? 1 : reads;
-}
-
-extern "C" int mrfa_conv2d_nhwc(void* stream, const mrfa_conv_params* pp) {
-    MRFA_CHECK_ARG(pp, "conv2d: null parameter block");
-    if (pp->groups > 1 && (pp->stats || pp->fin_scale || pp->bst_x || pp->in_scale))
-        MRFA_CHECK_ARG(mrfa_conv2d_groups_supported(pp), "conv2d: groups = %d is not implemented for these parameters (N = %d, %d x %d outputs, splitk %d): ask "
-                       "mrfa_conv2d_groups_supported() first", pp->groups, pp->N, pp->Hout, pp->Wout, pp->splitk);
-    if (pp->fin_scale) {
-        MRFA_CHECK_ARG(pp->stats && pp->fin_shift && pp->fin_gamma && pp->fin_beta && pp->fin_counter && pp->fin_count > 0,
-                       "conv2d: fin_scale needs stats, fin_shift, fin_gamma, fin_beta, fin_counter and fin_count > 0");
-        MRFA_CHECK_ARG((pp->fin_rmean == nullptr) == (pp->fin_rvar == nullptr), "conv2d: fin_rmean / fin_rvar come together");
-    }
-    if (pp->bst_x) {
-        MRFA_CHECK_ARG(pp->stats && pp->bst_scale && pp->bst_shift && pp->bst_mean && pp->bst_invstd && !pp->fin_scale,
-                       "conv2d: bst_x needs stats, bst_scale / _shift / _mean / _invstd and no fin_*");
-        MRFA_CHECK_ARG(mrfa_conv2d_bwdstats_supported(pp), "conv2d: bst_* is only implemented by the small-problem kernels: ask mrfa_conv2d_bwdstats_supported() first");
-    }
-    bool fin_done = false;
-    const int rc = conv2d_dispatch(stream, pp, &fin_done);
-    if (rc || !pp->fin_scale || fin_done) return rc;
-    // every kernel but the one-wave-per-tile one: the finalize launch behind the convolution, inside the call
-    return mrfa_bn_finalize_groups(stream, pp->stats, pp->fin_count, pp->fin_gamma, pp->fin_beta, pp->fin_rmean, pp->fin_rvar, pp->fin_momentum, pp->fin_eps,
-                                   pp->Cout, pp->groups > 1 ? pp->groups : 1, pp->fin_scale, pp->fin_shift, pp->fin_mean, pp->fin_invstd);
-}
-
-static int conv2d_dispatch(void* stream, const mrfa_conv_params* pp, bool* fin_done, int* dry_split, int* dry_reads_w) {
-    const mrfa_conv_params& p = *pp;
-    hipStream_t st = (hipStream_t)stream;
-    MRFA_CHECK_ARG(p.x && p.w && (p.y || dry_split), "conv2d: null pointer");
-    MRFA_CHECK_ARG(p.N > 0 && p.Cin > 0 && p.Cout > 0 && p.Hout > 0 && p.Wout > 0, "conv2d: bad sizes");
-    MRFA_CHECK_ARG(p.R >= 1 && p.S >= 1 && p.R <= 15 && p.S <= 15, "conv2d: kernel size %dx%d unsupported", p.R, p.S);
-    MRFA_CHECK_ARG((p.w_ld % 4) == 0 && aligned16(p.w), "conv2d: packed weight must be 16-B aligned, w_ld %% 4 == 0");
+// the row-tiled kernels: the split-K init pass, the tile, the split-K epilogue pass
+static int launch_rows(hipStream_t st, const mrfa_conv_params& p, const ConvPlan& c) {
     const bool flat = p.kflat > 0;
-    if (!flat) {
-        MRFA_CHECK_ARG((p.Cin % 32) == 0, "conv2d: chunked mode needs Cin %% 32 == 0 (got %d); use flat mode", p.Cin);
-        MRFA_CHECK_ARG((p.ldx % 4) == 0 && aligned16(p.x), "conv2d: chunked mode needs 16-B aligned x and ldx %% 4 == 0");
-        if (p.in_scale) MRFA_CHECK_ARG(aligned16(p.in_scale) && aligned16(p.in_shift), "conv2d: in_scale/in_shift alignment");
-    } else {
-        MRFA_CHECK_ARG(p.ktab != nullptr && aligned16(p.ktab), "conv2d: flat mode needs a 16-B aligned ktab");
-    }
-    const long long M = (long long)p.N * p.Hout * p.Wout;
-    const int Ktot = flat ? p.kflat : p.R * p.S * p.Cin;
-    const int KT = (Ktot + BK - 1) / BK;
+    const long long M = c.M;
     const int nb = p.nbatch > 1 ? p.nbatch : 1;
-
-    // ---- the keypoint encoder's <= 128-channel 3x3 layers in a split-operand mode: four-wave patches on the bf16 pipe (conv_lean.hip)
-    if (!flat && mrfa_conv_lean_eligible(p)) {
-        if (dry_split) { *dry_split = 1; if (dry_reads_w) *dry_reads_w = 0; return 0; }
-        g_last_tile = (32 << 16) | (32 << 4) | 4 | (1 << 27);    // bit 27: conv_lean
-        *fin_done = p.fin_scale != nullptr;                      // (finished by the launch's last workgroup)
-        return mrfa_conv_lean_launch(st, p);
-    }
-    // ---- 1x1 convolutions / linears of the keypoint encoder in a split-operand mode: K-pipelined four-wave tiles on the bf16 pipe (conv_lean.hip)
-    if (!flat && mrfa_gemm_lean_eligible(p, M)) {
-        if (dry_split) { *dry_split = 1; if (dry_reads_w) *dry_reads_w = 0; return 0; }
-        g_last_tile = (64 << 16) | (64 << 4) | 4 | (1 << 26);    // bit 26: gemm_lean
-        *fin_done = p.fin_scale != nullptr;                      // (finished by the launch's last workgroup)
-        return mrfa_gemm_lean_launch(st, p, M);
-    }
-    // ---- small problems (the MTIA prior's 0.1-0.6 GFLOP layers): one wave per output tile, no LDS / barrier / split-K (conv_small.hip)
-    static const bool small_on = [] { const char* e = getenv("MRFA_CONV_SMALL"); return !(e && e[0] == '0'); }();
-    if (small_on && mrfa_tuning_conv_small() && mrfa_conv_small_eligible(p, M)) {
-        if (dry_split) { *dry_split = 1; return 0; }
-        g_last_tile = (16 << 16) | (16 << 4) | 8;                // bit 3: conv_small
-        *fin_done = p.fin_scale != nullptr;                      // (finished by the launch's last workgroup)
-        return mrfa_conv_small_launch(st, p, M);
-    }
-    if (p.stride < 0 || p.stride > 2 || (p.stride == 2 && !(flat && !p.ups && p.nbatch <= 1))) {
-        mrfa_set_error("conv2d: stride = %d is only implemented by the one-wave-per-tile kernel and by flat-K launches: ask mrfa_conv2d_stride_supported() first", p.stride);
-        return 1;
-    }
-    if (p.mask && !(!flat && mrfa_conv_halo_eligible(p))) {
-        mrfa_set_error("conv2d: `mask` is only honoured by the patch-tiled kernel: ask mrfa_conv2d_mask_supported() first");
-        return 1;
-    }
-    if (p.ups == 2 && !(!flat && mrfa_conv_halo_eligible(p))) {
-        mrfa_set_error("conv2d: ups = 2 (phase data gradient of a fused-upsample layer) is only implemented for the shapes "
-                       "mrfa_conv2d_phase_dgrad_supported() reports");
-        return 1;
-    }
-    // ---- 3x3 stride-1 layers with 32-aligned rows in split-operand mode: patch-tiled kernel, input halo split once per chunk (conv_halo.hip)
-    if (!flat && mrfa_conv_halo_eligible(p)) {
-        if (dry_split) { *dry_split = 1; if (dry_reads_w) *dry_reads_w = 0; return 0; }
-        *fin_done = p.fin_scale != nullptr;                      // (finished by the launch's last workgroup, common.h: fused_bn_finalize)
-        g_last_tile = (128 << 16) | ((p.Cout <= 64 ? 64 : 128) << 4) | 4 | (1 << 28);       // bit 28: conv_halo
-        return mrfa_conv_halo_launch(st, p);
-    }
-    // ---- tile selection: largest BN whose padding waste is small, then BM by how many workgroups result
-    int BN = 128;
-    {
-        const int cands[4] = {128, 96, 64, 32};
-        const double pen[4] = {1.0, 1.08, 1.16, 1.3};       // measured per-tile efficiency relative to 128x128
-        double best = 1e18;
-        for (int i = 0; i < 4; ++i) {
-            if (cands[i] == 96 && flat) continue;
-            const double cost = (double)cdiv(p.Cout, cands[i]) * cands[i] * pen[i];
-            if (cost < best) { best = cost; BN = cands[i]; }
-        }
-    }
-    // split-operand mode: the bf16x6 kernel only exists as a 128-wide tile and is ~1.5x faster than the fp32-MFMA tiles, which
-    // outweighs the padding of 64 / 96 / 160 / 192-channel outputs to a multiple of 128
-    if (g_mfma_mode >= 1 && !flat && p.Cout >= 32) BN = p.Cout <= 64 ? 64 : 128;
-    auto ntiles = [&](int bm, int bn) { return ((M + bm - 1) / bm) * cdiv(p.Cout, bn) * nb; };
-    // Few output tiles (low-resolution hourglass / generator levels): every M-tile re-reads the whole weight tensor, so
-    // keep the tile tall and split K across workgroups first; shrink BM only when K is too short to split.
-    int BM = 128;
-    if (BN == 96 && ntiles(128, 96) < 384) BN = 128;     // few tiles: the 128-wide family has the 64/32-row variants
-    if (BN == 128) { if (M <= 32) BM = 32; else if (M <= 64) BM = 64; }
-    else if (BN == 64 && M <= 64) BM = 64;
-    int splitk = 1;
-    const bool auto_split = (p.splitk == 0);
-    if (p.splitk > 1) splitk = p.splitk;
-    {
-        // Short K loop over many pixels (HRNet's 32..64-channel 3x3 convs at 64^2 / 32^2): a K split would add a zero-init and
-        // a reduction/epilogue pass over the whole output (2 x 20 us measured) to a 20 us kernel -- keep one launch
-        const bool short_k_big_m = KT < 32 && M > 4096;
-        const bool grouped_stats = p.groups > 1 && p.stats && !(p.sk_ticket && !p.accumulate);       // (the split-K epilogue PASS does not keep statistic groups apart; the fused one does)
-        const int max_split = (auto_split && !short_k_big_m && !grouped_stats) ? (KT / 2 > 0 ? KT / 2 : 1) : 1;
-        long long t = ntiles(BM, BN);
-        // (round 4, tools/sweep_splitk.py: with the split forced per launch the automatic choice is within 10 % of the best on six of eight low-resolution
-        // shapes -- 128 -> 32 @64^2 fused upsample would prefer no split (74 -> 54 us), 256 -> 512 @8^2 a quarter of the slices (40 -> 30 us).  Lowering the
-        // target here to catch those two moved OTHER layers onto the 64-row fp32 tiles through the BM loop below: +0.8 ms per step.  Left as it was.)
-        if (t < 384 && !(short_k_big_m && t >= 128)) {
-            // 512 workgroups -- or 256 for the deep-K launches that finish their split themselves (sk_ticket): their partial sums pass the memory-side atomic
-            // units in one burst behind the k-loop (12 + 6 us of a 51 us launch, profiles/r6_splitk_launch_timeline.txt), and with the 128-row tile kept half the
-            // slices are 5-6 us faster on 8 <= t <= 16 tiles (tools/sweep_splitk.py TILE128=1 COLD=1 FUSED=1: 1024 -> 1024 @4^2 52.3 -> 47.1, 512 -> 512 @8^2
-            // 51.4 -> 46.7, 1024 -> 256 @8^2 up 53.0 -> 46.5, 256 -> 512 @8^2 42.8 -> 36.0)
-            const bool half_target = g_split_target_256 && auto_split && p.sk_ticket && !p.accumulate && KT >= 72 && KT <= 320 && BM == 128 && t >= 8 && t <= 16;      // (deeper K: 2048 -> 512 @8^2 up wants its 32 slices, 86 against 101 us)
-            int want = (int)(((half_target ? 256 : 512) + t - 1) / t);
-            if (auto_split) splitk = want <= max_split ? want : max_split;
-            const int min_bm = (BN == 128) ? 32 : (BN == 64 ? 64 : 128);
-            while (!half_target && ntiles(BM, BN) * splitk < 384 && BM > min_bm) {
-                BM >>= 1;
-                if (auto_split) {
-                    t = ntiles(BM, BN);
-                    want = (int)((512 + t - 1) / t);
-                    splitk = want <= max_split ? want : max_split;
-                }
-            }
-            if (splitk < 1) splitk = 1;
-        }
-    }
-    bool w8 = false;                                         // 8-wave (512-thread) variant of the 128x128 tile
-    if (p.tile) {
-        BM = p.tile >> 16; BN = p.tile & 0x7fff; w8 = (p.tile & 0x8000) != 0;
-        if (p.splitk >= 1) splitk = p.splitk;
-    }
-    if (dry_split) {
-        *dry_split = splitk;
-        // (the row-tiled split-operand tile copies pre-split weight planes when it has them -- except in plain-bf16 mode, which rounds the fp32 layout itself)
-        if (dry_reads_w) *dry_reads_w = !(g_mfma_mode >= 1 && g_mfma_mode != 3 && BM == 128 && (BN == 128 || BN == 64) && !flat && p.w_split);
-        return 0;
-    }
-    // v8: with sk_ticket the tile's last workgroup applies bias / affine / residual / ReLU / statistics (no epilogue pass); with y_zero the output already holds
-    // zeros (no init pass: the bias then comes with the fused epilogue)
-    const bool fused = splitk > 1 && p.sk_ticket && !p.accumulate;
+    const int splitk = c.splitk;
     mrfa_conv_params pk = p;                                 // what the kernels see
     if (splitk > 1) {
-        const bool init = !p.accumulate && !(p.y_zero && (fused || !p.bias));
+        // with y_zero the output already holds zeros (no init pass: the bias then comes with the fused epilogue)
+        const bool init = !p.accumulate && !(p.y_zero && (c.fused || !p.bias));
         if (init) {
             const long long rows = M * nb;
             MRFA_CHECK_ARG(nb == 1 || p.y_bs == (long long)M * p.ldy, "conv2d: split-K batched output must be dense");
@@ -602,19 +398,15 @@ static int conv2d_dispatch(void* stream, const mrfa_conv_params* pp, bool* fin_d
             MRFA_CHECK_LAUNCH("splitk_init");
             pk.bias = nullptr;                               // (written by the init pass)
         }
-        if (!fused) pk.sk_ticket = nullptr;
+        if (!c.fused) pk.sk_ticket = nullptr;
     }
-    // the BatchNorm that follows (fin_*): finished by the launch's last workgroup, except behind a K split with an epilogue pass and in batched launches
-    if (p.fin_scale && nb == 1 && (splitk == 1 || fused)) *fin_done = true;
-    else pk.fin_scale = nullptr;
-    g_last_tile = (BM << 16) | (BN << 4) | ((flat ? 1 : 0) << 1) | (splitk > 1 ? 1 : 0);
+    if (!c.fin_in_launch) pk.fin_scale = nullptr;
+    g_last_tile = c.last_config;
+    const int BM = c.BM, BN = c.BN;
     int rc = 1;
-#define CFG(bm, bn, wm, wn) if (BM == bm && BN == bn) rc = launch_cfg<bm, bn, wm, wn>(st, pk, KT, M, splitk)
-    if (!p.tile && BM == 128 && BN == 128 && !flat) w8 = true;      // 8 waves: 4 waves/SIMD hide the load/barrier phases (+4..13 %)
-    if (g_mfma_mode >= 1 && BM == 128 && (BN == 128 || BN == 64) && !flat) {
-        g_last_tile |= 4;                                            // bit 2: split-operand kernel
-        rc = mrfa_conv_split_launch(st, pk, KT, M, splitk, BN);
-    } else if (w8 && BM == 128 && BN == 128) rc = launch_cfg<128, 128, 2, 4>(st, pk, KT, M, splitk);
+#define CFG(bm, bn, wm, wn) if (BM == bm && BN == bn) rc = launch_cfg<bm, bn, wm, wn>(st, pk, c.KT, M, splitk)
+    if (c.family == ConvFamily::rows_split) rc = mrfa_conv_split_launch(st, pk, c.KT, M, splitk, BN);
+    else if (c.w8 && BM == 128 && BN == 128) rc = launch_cfg<128, 128, 2, 4>(st, pk, c.KT, M, splitk);
     else CFG(128, 128, 2, 2);
     else CFG(128, 96, 4, 1);
     else CFG(128, 64, 2, 2);
@@ -625,7 +417,7 @@ static int conv2d_dispatch(void* stream, const mrfa_conv_params* pp, bool* fin_d
     else { mrfa_set_error("conv2d: no tile config %dx%d", BM, BN); return 1; }
 #undef CFG
     if (rc) return rc;
-    if (splitk > 1 && !fused && (p.relu || p.stats || p.out_scale || p.res)) {
+    if (splitk > 1 && !c.fused && (p.relu || p.stats || p.out_scale || p.res)) {
         MRFA_CHECK_ARG(!p.accumulate, "conv2d: split-K with accumulate cannot apply an epilogue");
         const long long rows = M * nb;
         dim3 grid(cdiv(p.Cout, 64), (unsigned)(rows < 256 ? rows : 256));
@@ -634,4 +426,38 @@ static int conv2d_dispatch(void* stream, const mrfa_conv_params* pp, bool* fin_d
         MRFA_CHECK_LAUNCH("splitk_epilogue");
     }
     return 0;
+}
+
+extern "C" int mrfa_conv2d_nhwc(void* stream, const mrfa_conv_params* pp) {
+    MRFA_CHECK_ARG(pp, "conv2d: null parameter block");
+    const mrfa_conv_params& p = *pp;
+    hipStream_t st = (hipStream_t)stream;
+    const ConvPlan c = plan_conv(p);
+    MRFA_CHECK_ARG(c.groups_ok, "conv2d: groups = %d is not implemented for these parameters (N = %d, %d x %d outputs, splitk %d): ask "
+                   "mrfa_conv2d_groups_supported() first", p.groups, p.N, p.Hout, p.Wout, p.splitk);
+    if (p.fin_scale) {
+        MRFA_CHECK_ARG(p.stats && p.fin_shift && p.fin_gamma && p.fin_beta && p.fin_counter && p.fin_count > 0,
+                       "conv2d: fin_scale needs stats, fin_shift, fin_gamma, fin_beta, fin_counter and fin_count > 0");
+        MRFA_CHECK_ARG((p.fin_rmean == nullptr) == (p.fin_rvar == nullptr), "conv2d: fin_rmean / fin_rvar come together");
+    }
+    if (p.bst_x) {
+        MRFA_CHECK_ARG(p.stats && p.bst_scale && p.bst_shift && p.bst_mean && p.bst_invstd && !p.fin_scale,
+                       "conv2d: bst_x needs stats, bst_scale / _shift / _mean / _invstd and no fin_*");
+        MRFA_CHECK_ARG(c.bst_ok, "conv2d: bst_* is only implemented by the small-problem kernels: ask mrfa_conv2d_bwdstats_supported() first");
+    }
+    MRFA_CHECK_ARG(p.y, "conv2d: null pointer");
+    if (c.family == ConvFamily::refused) { mrfa_set_error("%s", c.error); return 1; }
+    int rc;
+    switch (c.family) {
+        case ConvFamily::lean: g_last_tile = c.last_config; rc = mrfa_conv_lean_launch(st, p, c.lean_geo); break;
+        case ConvFamily::gemm_lean: g_last_tile = c.last_config; rc = mrfa_gemm_lean_launch(st, p, c.M, c.gemm_cfg); break;
+        case ConvFamily::small: g_last_tile = c.last_config; rc = mrfa_conv_small_launch(st, p, c.M, c.small_tm, c.small_tn); break;
+        case ConvFamily::halo:
+        case ConvFamily::halo_dgrad: g_last_tile = c.last_config; rc = mrfa_conv_halo_launch(st, p, c.halo); break;
+        default: rc = launch_rows(st, p, c); break;
+    }
+    if (rc || !p.fin_scale || c.fin_in_launch) return rc;
+    // every kernel but the one-wave-per-tile one: the finalize launch behind the convolution, inside the call
+    return mrfa_bn_finalize_groups(stream, p.stats, p.fin_count, p.fin_gamma, p.fin_beta, p.fin_rmean, p.fin_rvar, p.fin_momentum, p.fin_eps,
+                                   p.Cout, p.groups > 1 ? p.groups : 1, p.fin_scale, p.fin_shift, p.fin_mean, p.fin_invstd);
 }

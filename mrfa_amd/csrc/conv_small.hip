@@ -252,15 +252,9 @@ bool mrfa_conv_small_eligible(const mrfa_conv_params& p, long long M) {
     return true;
 }
 
-int mrfa_conv_small_launch(hipStream_t st, const mrfa_conv_params& p, long long M) {
-    // wave tile: the largest of 32x32 / 16x32 / 16x16 that still yields >= ~2 000 waves (two per SIMD: measured best once the loads coalesce)
+// (tm x tn) x 16 rows / columns per wave: plan_conv's wave tile
+int mrfa_conv_small_launch(hipStream_t st, const mrfa_conv_params& p, long long M, int tm, int tn) {
     const int ncols = (p.Cout + 15) / 16 * 16;
-    auto waves = [&](int wm, int wn) { return ((M + wm - 1) / wm) * ((ncols + wn - 1) / wn); };
-    int tm = 2, tn = 2;
-    if (waves(32, 32) < 2048) { tm = 1; tn = 2; }
-    if (tm == 1 && waves(16, 32) < 2048) { tn = 1; }
-    if (ncols % 32 != 0 && tn == 2 && ncols < 32) tn = 1;
-    if (p.groups > 1 && tm == 2 && (group_rows(p, M) % 128) != 0) tm = 1;       // (eligibility guarantees % 64)
     const int WM = 16 * tm, WN = 16 * tn;
     const int tiles_n = (ncols + WN - 1) / WN;
     const int wave_tiles_m = (int)((M + WM - 1) / WM);

@@ -392,41 +392,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     }
 }
 
-int g_wgrad_halo_on = -1;
-int g_wgrad_halo_min = 192;
-int g_wgrad_halo_target = 256;      // workgroups per round (one per CU)
-int g_wgrad_halo_phase = 1;         // weight gradient of fused-upsample layers in phase form
-
 }  // namespace
-
-int mrfa_tuning_wgrad_halo(int set) {
-    if (g_wgrad_halo_on < 0) { const char* e = getenv("MRFA_WGRAD_HALO"); g_wgrad_halo_on = !(e && e[0] == '0'); }
-    const int prev = g_wgrad_halo_on;
-    if (set >= 0) g_wgrad_halo_on = set != 0;
-    return prev;
-}
-
-int mrfa_tuning_wgrad_halo_min(int set) {
-    const int prev = g_wgrad_halo_min;
-    if (set >= 0) g_wgrad_halo_min = set;
-    return prev;
-}
-
-int mrfa_tuning_wgrad_halo_phase(int set) {
-    const int prev = g_wgrad_halo_phase;
-    if (set >= 0) g_wgrad_halo_phase = set != 0;
-    return prev;
-}
-
-int mrfa_tuning_wgrad_halo_target(int set) {
-    const int prev = g_wgrad_halo_target;
-    if (set > 0) g_wgrad_halo_target = set;
-    return prev;
-}
 
 // fused-upsample layer whose LOW-resolution grid tiles into 32-pixel strips: phase form (wgrad_halo_kernel<..., PH = true>)
 static bool wgrad_halo_phase(const mrfa_wgrad_params& p) {
-    return g_wgrad_halo_phase && p.ups == 1 && !p.in_scale && (p.Win % 32) == 0 && p.Hin >= 8;
+    return g_tune.wgrad_halo_phase && p.ups == 1 && !p.in_scale && (p.Win % 32) == 0 && p.Hin >= 8;
 }
 
 static void wgrad_halo_config(const mrfa_wgrad_params& p, int& NBO, int& HS, int& segs_y, long long& total) {
@@ -444,7 +414,7 @@ static void wgrad_halo_config(const mrfa_wgrad_params& p, int& NBO, int& HS, int
     double best = 1e30;
     for (int hs = Hg; hs >= 8; hs /= 2) {
         const long long tot = cols * ntiles * cdiv(Hg, hs);
-        const double cost = (double)((tot + g_wgrad_halo_target - 1) / g_wgrad_halo_target) * (hs + 6);
+        const double cost = (double)((tot + g_tune.wgrad_halo_target_wgs - 1) / g_tune.wgrad_halo_target_wgs) * (hs + 6);
         if (cost < best) { best = cost; HS = hs; }
         if (hs % 2) break;
     }
@@ -454,7 +424,7 @@ static void wgrad_halo_config(const mrfa_wgrad_params& p, int& NBO, int& HS, int
 
 bool mrfa_wgrad_halo_eligible(const mrfa_wgrad_params& p) {
     const int mode = mrfa_get_mfma_mode();
-    if (!mrfa_tuning_wgrad_halo(-1) || (mode != 1 && mode != 2 && mode != 3)) return false;
+    if (!g_tune.wgrad_halo || (mode != 1 && mode != 2 && mode != 3)) return false;
     if (p.kflat > 0 || p.R != 3 || p.S != 3 || p.pad != 1 || p.nbatch > 1 || p.ksplit > 0) return false;
     if ((p.Wout % 32) != 0 || (p.Cin % 32) != 0 || p.Cout < 32 || p.Hout < 8) return false;
     if (p.Hout != (p.Hin << p.ups) || p.Wout != (p.Win << p.ups)) return false;
@@ -464,7 +434,7 @@ bool mrfa_wgrad_halo_eligible(const mrfa_wgrad_params& p) {
     int NBO, HS, segs_y;
     long long total;
     wgrad_halo_config(p, NBO, HS, segs_y, total);
-    return total >= g_wgrad_halo_min;                  // too few workgroups: the per-tap kernel splits the pixel range finer
+    return total >= g_tune.wgrad_halo_min_wgs;                  // too few workgroups: the per-tap kernel splits the pixel range finer
 }
 
 int mrfa_wgrad_halo_launch(hipStream_t st, const mrfa_wgrad_params& p) {

@@ -311,8 +311,6 @@ __global__ __launch_bounds__(256, 1) void wgrad_lean_kernel(const LeanWMulti a) 
             }
 }
 
-int g_wgrad_lean_on = -1;
-
 template <int NB, int TW>
 constexpr size_t wl_lds(int npc) {
     constexpr int NPXW = NB == 1 ? 4 : 1, TR = 32 / TW, PR = NPXW * TR, HP = TW + 2, HPIX = (PR + 2) * HP, DPIX = NPXW * 32;
@@ -349,17 +347,10 @@ int wl_launch(hipStream_t st, const LeanWMulti& m, bool pro, int mode) {
 
 }  // namespace
 
-int mrfa_tuning_wgrad_lean(int set) {
-    if (g_wgrad_lean_on < 0) { const char* e = getenv("MRFA_WGRAD_LEAN"); g_wgrad_lean_on = !(e && e[0] == '0'); }
-    const int prev = g_wgrad_lean_on;
-    if (set >= 0) g_wgrad_lean_on = set != 0;
-    return prev;
-}
-
 // 1: the problem runs here: 3x3 / pad 1 / stride 1, 32 -> 32 channels or 64-aligned channel counts up to 128, 16-byte addressable rows, no bias gradient
 bool mrfa_wgrad_lean_eligible(const mrfa_wgrad_params& p) {
     const int mode = mrfa_get_mfma_mode();
-    if (!mrfa_tuning_wgrad_lean(-1) || (mode != 1 && mode != 2 && mode != 3)) return false;
+    if (!g_tune.wgrad_lean || (mode != 1 && mode != 2 && mode != 3)) return false;
     if (p.kflat > 0 || p.ups || p.R != 3 || p.S != 3 || p.pad != 1 || p.nbatch > 1 || p.ksplit > 0 || p.stride > 1 || p.dbias) return false;
     if (p.Hout != p.Hin || p.Wout != p.Win || p.Cin > 128 || p.Cout > 128) return false;
     if ((p.ldx % 4) != 0 || !aligned16(p.x) || (p.ldy % 4) != 0 || !aligned16(p.dy)) return false;

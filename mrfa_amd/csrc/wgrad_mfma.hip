@@ -363,36 +363,21 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ ws, float* __restr
 
 }  // namespace
 
-extern "C" int mrfa_conv2d_wgrad_lean_supported(const mrfa_wgrad_params* p) { return p && mrfa_wgrad_lean_eligible(*p) ? 1 : 0; }
-
-extern "C" int mrfa_conv2d_wgrad_groups_supported(const mrfa_wgrad_params* p) {
-    if (!p || p->groups <= 1 || !p->in_scale) return p ? 1 : 0;
-    return mrfa_wgrad_lean_eligible(*p) ? 1 : 0;
-}
-
 extern "C" int mrfa_conv2d_wgrad_nhwc(void* stream, const mrfa_wgrad_params* pp) {
     const mrfa_wgrad_params& p = *pp;
     hipStream_t st = (hipStream_t)stream;
-    MRFA_CHECK_ARG(p.x && p.dy && p.dw, "wgrad: null pointer");
+    const WgradPlan c = plan_wgrad(p);
+    const long long M = c.M;
+    switch (c.family) {
+        case WgradFamily::refused: mrfa_set_error("%s", c.error); return 1;
+        case WgradFamily::lean: { unsigned char taken = 0; return mrfa_wgrad_lean_multi(st, &p, 1, &taken); }
+        case WgradFamily::small: return mrfa_wgrad_small_launch(st, p, M);
+        case WgradFamily::halo: return mrfa_wgrad_halo_launch(st, p);
+        case WgradFamily::tiled: break;
+    }
     const int dy_scalar = ((p.ldy % 4) == 0 && aligned16(p.dy) && (p.dy_bs % 4) == 0) ? 0 : 1;
     const bool flat = p.kflat > 0;
-    if (!flat) MRFA_CHECK_ARG((p.ldx % 4) == 0 && aligned16(p.x), "wgrad: x must be a 16-B aligned view with ld %% 4 == 0");
-    else MRFA_CHECK_ARG(p.ktab != nullptr, "wgrad: flat mode needs ktab");
-    const long long M = (long long)p.N * p.Hout * p.Wout;
-    MRFA_CHECK_ARG(M < (1ll << 31) - 64, "wgrad: too many pixels");
     const int nb = p.nbatch > 1 ? p.nbatch : 1;
-    // the keypoint encoder's <= 128-channel 3x3 layers WITH a prologue (a residual block's second convolution reading the raw output of its first): the
-    // all-taps kernel of wgrad_lean.hip as a one-problem launch (without a prologue a lone problem stays on wgrad_small.hip: its 2 000 waves fill the chip)
-    if (p.in_scale && mrfa_wgrad_lean_eligible(p)) {
-        unsigned char taken = 0;
-        return mrfa_wgrad_lean_multi(st, &p, 1, &taken);
-    }
-    MRFA_CHECK_ARG(p.groups <= 1 || !p.in_scale, "wgrad: groups = %d with a prologue is only implemented where mrfa_conv2d_wgrad_groups_supported() says so", p.groups);
-    // small problems (the MTIA prior's layers): one wave per 32 x 32 weight block, no LDS staging, in-workgroup reduction (wgrad_small.hip)
-    static const bool small_on = [] { const char* e = getenv("MRFA_CONV_SMALL"); return !(e && e[0] == '0'); }();
-    if (small_on && mrfa_tuning_conv_small() && mrfa_wgrad_small_eligible(p, M)) return mrfa_wgrad_small_launch(st, p, M);
-    MRFA_CHECK_ARG(p.stride <= 1, "wgrad: stride = %d is only implemented by the small-problem kernel: ask mrfa_conv2d_wgrad_stride_supported() first", p.stride);
-    if (!flat && mrfa_wgrad_halo_eligible(p)) return mrfa_wgrad_halo_launch(st, p);      // 3x3 stride-1 layers: all nine taps per staging (wgrad_halo.hip)
     int taps = flat ? 1 : p.R * p.S;
     const int NTOT = flat ? p.kflat : p.Cin;
     // tile selection: (BM over Cout) x (BN over Cin or taps*Cin)

@@ -303,12 +303,6 @@ bool mrfa_wgrad_small_eligible(const mrfa_wgrad_params& p, long long M) {
     return true;
 }
 
-extern "C" int mrfa_conv2d_wgrad_stride_supported(const mrfa_wgrad_params* p) {
-    if (!p || p->stride != 2) return 0;
-    if (p->Hout != (p->Hin + 2 * p->pad - p->R) / 2 + 1 || p->Wout != (p->Win + 2 * p->pad - p->S) / 2 + 1) return 0;
-    return mrfa_wgrad_small_eligible(*p, (long long)p->N * p->Hout * p->Wout) ? 1 : 0;
-}
-
 int mrfa_wgrad_small_launch(hipStream_t st, const mrfa_wgrad_params& p, long long M) {
     SmallProblem sp;
     const int variant = small_problem(p, M, &sp);
@@ -332,7 +326,6 @@ int mrfa_wgrad_small_launch(hipStream_t st, const mrfa_wgrad_params& p, long lon
 extern "C" int mrfa_conv2d_wgrad_multi(void* stream, const mrfa_wgrad_params* ps, int n) {
     MRFA_CHECK_ARG(n >= 0 && (n == 0 || ps), "wgrad_multi: bad args");
     hipStream_t st = (hipStream_t)stream;
-    static const bool small_on = [] { const char* e = getenv("MRFA_CONV_SMALL"); return !(e && e[0] == '0'); }();
     SmallMulti batch[SMALL_VARIANTS];
     for (int v = 0; v < SMALL_VARIANTS; ++v) { batch[v].n = 0; batch[v].prefix[0] = 0; }
     auto flush = [&](int v) -> int {
@@ -360,7 +353,7 @@ extern "C" int mrfa_conv2d_wgrad_multi(void* stream, const mrfa_wgrad_params* ps
         const mrfa_wgrad_params& p = ps[i];
         MRFA_CHECK_ARG(p.x && p.dy && p.dw && p.N > 0 && p.Hout > 0 && p.Wout > 0, "wgrad_multi: problem %d: null pointer / bad sizes", i);
         const long long M = (long long)p.N * p.Hout * p.Wout;
-        if (!(small_on && mrfa_tuning_conv_small() && mrfa_wgrad_small_eligible(p, M))) {
+        if (!plan_wgrad(p).small) {
             const int rc = mrfa_conv2d_wgrad_nhwc(stream, &p);
             if (rc) return rc;
             continue;

@@ -378,6 +378,13 @@ def _r4(c: int) -> int:
     return (c + 3) // 4 * 4
 
 
+def _conv_params() -> hip.ConvParams:
+    """the parameter block of one conv launch, with FORCE_TILE already in it: every capability query asked about the block then sees the launch's tile"""
+    p = hip.ConvParams()
+    p.tile = FORCE_TILE
+    return p
+
+
 # ------------------------------------------------------------------------------------------------- storage / views
 class Storage:
     """[rows, ld] fp32 buffer + lazily allocated gradient buffer of the same geometry."""
@@ -973,8 +980,6 @@ class Ctx:
             self.tape.append(fn)
 
     def _launch_conv(self, p, what: str, alg_cin: Optional[int] = None):
-        if FORCE_TILE:
-            p.tile = FORCE_TILE
         prof = Ctx.profile
         if prof is None:
             self._chk(self.L.mrfa_conv2d_nhwc(self.s, C.byref(p)), what)
@@ -1094,7 +1099,7 @@ class Ctx:
                 if cw not in self.touched_convs:
                     self.touched_convs.append(cw)
             return out
-        p = hip.ConvParams()
+        p = _conv_params()
         p.x, p.ldx, p.Hin, p.Win, p.ups, p.N, p.Cin = x.ptr, x.ld, x.H, x.W, int(ups), x.N, cw.Cin
         padded = cw.fwd_flat and x.zpad and x.coff % 4 == 0 and pre is None
         cop = (cw.Cout + 127) // 128 * 128
@@ -1285,7 +1290,7 @@ class Ctx:
                 and x.coff % 4 == 0):
             # UpBlock2d: data gradient in phase form (four transposed 2x2 convolutions of the phase images of dY, csrc/conv_halo.hip MODE 2)
             # straight into x.grad -- instead of the 3x3 data gradient on the 2H x 2W grid + the 2x2 sum-pooling pass
-            q = hip.ConvParams()
+            q = _conv_params()
             q.x, q.ldx, q.Hin, q.Win, q.ups, q.N, q.Cin = out.gptr, out.ld, out.H, out.W, 2, out.N, cw.Cout
             cipd = (cw.Cin + 127) // 128 * 128
             wph, q.w_phase_piece = cw.phase_pack(dgrad=True)
@@ -1303,7 +1308,7 @@ class Ctx:
                 self._launch_conv(q, "dgrad(phase)", cw.Cout)
                 return
         tgt = x if direct else self.new(x.N, Hv, Wv, cw.Cin)
-        p = hip.ConvParams()
+        p = _conv_params()
         p.x, p.ldx, p.Hin, p.Win, p.ups, p.N, p.Cin = out.gptr, out.ld, out.H, out.W, 0, out.N, cw.Cout
         co32 = (cw.Cout + 31) // 32 * 32
         # Cout % 32 != 0 but the dY view sits in a wider (zero-initialised, finite) gradient buffer: read it as co32
@@ -2037,7 +2042,7 @@ class Ctx:
         data gradient stays the stride-1 one over the zero-stuffed dY.  None: the library has no strided kernel for this shape."""
         Ho, Wo = (x.H + 2 * cw.pad - cw.R) // 2 + 1, (x.W + 2 * cw.pad - cw.S) // 2 + 1
         cop = (cw.Cout + 127) // 128 * 128
-        p = hip.ConvParams()
+        p = _conv_params()
         p.x, p.ldx, p.Hin, p.Win, p.ups, p.N, p.Cin = x.ptr, x.ld, x.H, x.W, 0, x.N, cw.Cin
         if cw.fwd_flat:                                # few input channels (the 3 -> 64 stem, hr_base.py:302): the fp32 tile kernel's flat-K gather, strided
             p.w_ld, p.w_tap, p.kflat, p.w_rows = (cw.T * cw.Cin + 31) // 32 * 32, 0, cw.T * cw.Cin, cop
@@ -2200,7 +2205,7 @@ class Ctx:
     # -- GEMMs for the correlation volume -----------------------------------------------------------------------
     def gemm_nt(self, a_ptr, lda, b_ptr, ldb, c_ptr, ldc, M, Nn, K, alpha, nbatch, a_bs, b_bs, c_bs, accumulate=False):
         """C[b] (=|+=) alpha * A[b] (M x K, k contiguous) @ B[b]^T (Nn x K, k contiguous)"""
-        p = hip.ConvParams()
+        p = _conv_params()
         p.x, p.ldx, p.Hin, p.Win, p.ups, p.N, p.Cin = a_ptr, lda, 1, M, 0, 1, K
         p.w, p.w_ld, p.w_tap, p.w_rows = b_ptr, ldb, 0, Nn
         p.y, p.ldy, p.Cout, p.Hout, p.Wout = c_ptr, ldc, Nn, 1, M
