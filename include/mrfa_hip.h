@@ -43,8 +43,10 @@ const char* mrfa_last_error(void);
  *      encoder's <= 128-channel 3x3 layers (conv_lean.hip; mrfa_conv2d_last_config() bit 27; it honours in_scale / in_shift, stats / fin_* / bst_* / groups),
  *      tuning keys "conv_lean", "conv_lean_min_wgs", "conv_lean_geo"; mrfa_wgrad_params += groups with mrfa_conv2d_wgrad_groups_supported(); with
  *      groups > 1 the prologue vectors in_scale / in_shift of mrfa_conv_params are [groups][Cin] (only where mrfa_conv2d_groups_supported() says so:
- *      conv_lean.hip); all-taps multi-problem weight gradient of the same layers (wgrad_lean.hip, tuning key "wgrad_lean").                               */
-#define MRFA_ABI_VERSION 9
+ *      conv_lean.hip); all-taps multi-problem weight gradient of the same layers (wgrad_lean.hip, tuning key "wgrad_lean").
+ *  10  bf16 activation STORAGE, first slice: mrfa_cast_bf16() and mrfa_grid_sample_bf16_fwd() (the source-feature cache of the animation loop; no struct
+ *      changed: a version-9 client still works against this library, not the reverse).                                                                    */
+#define MRFA_ABI_VERSION 10
 int mrfa_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -362,6 +364,11 @@ int mrfa_grid_sample_bwd(void* stream, const float* in, int ldi, long long in_bs
                          const float* grid, int ldg, int N, int Ho, int Wo, const float* dout, int lddo, int mode,
                          float* din /*+= atomics, may be null*/, int lddi, long long din_bstride,
                          float* dgrid /*+= , may be null*/, int lddg);
+/* v10: the forward on a bf16 input (raw bf16 words; ldi / in_bstride count bf16 elements), grid and output fp32: the result of mrfa_grid_sample_fwd on the
+ * widened input (same taps, same selection, same fp32 blend in the same order).  Forward only: the input is an inference cache.  Needs C % 8 == 0,
+ * ldi % 8 == 0, in_bstride % 8 == 0, ldo % 4 == 0 and 16-byte aligned in / out; anything else is an argument error (no slow path).                  */
+int mrfa_grid_sample_bf16_fwd(void* stream, const unsigned short* in, int ldi, long long in_bstride, int in_rep, int Hi, int Wi, int C,
+                              const float* grid, int ldg, int N, int Ho, int Wo, float* out, int ldo, int mode);
 
 /* v6: Transform.transform_frame (model.py:44-48): bilinear F.grid_sample(frame, grid, padding_mode="reflection") with align_corners=False on NCHW frames
  * (N,C,H,W) -> (N,C,Ho,Wo); grid (N,Ho,Wo,2) contiguous, normalised (x, y).  Forward only: nothing differentiates through the equivariance warp.   */
@@ -412,6 +419,9 @@ int mrfa_bias_act(void* stream, const float* x, int ldx, long long rows, int C, 
 int mrfa_act_bwd(void* stream, const float* y, int ldy, const float* dy, int lddy, long long rows, int C, int act,
                  float* dx, int lddx, int accumulate);
 int mrfa_copy_view(void* stream, const float* x, int ldx, long long rows, int C, float* y, int ldy, float mul, int accumulate);
+/* v10: y = bf16(x) on views, round to nearest, ties to even; a NaN stays a NaN.  Needs C % 8 == 0, ldx % 8 == 0, ldy % 8 == 0 (ldy in bf16 elements) and
+ * 16-byte aligned pointers; anything else is an argument error.                                                                                      */
+int mrfa_cast_bf16(void* stream, const float* x, int ldx, long long rows, int C, unsigned short* y, int ldy);
 /* y = a*occ + b*(1-occ) on NHWC views with a 1-channel occ  (generator.py:47,57,63)                              */
 int mrfa_blend_fwd(void* stream, const float* a, int lda, const float* b, int ldb, const float* occ, int ldo,
                    long long rows, int C, float* y, int ldy);

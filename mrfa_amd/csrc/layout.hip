@@ -145,6 +145,32 @@ __global__ void copy_view_vec_kernel(const float* __restrict__ x, int ldx, int C
     }
 }
 
+// fp32 view -> bf16 view, round to nearest, ties to even (the arithmetic of rne16 in conv_halo.hip; a NaN stays a NaN: the rounding carry would turn a
+// payload that sits in the low 16 bits into an infinity).  Streaming: a lane loads eight values (2 x 16 bytes) and stores them as one 16-byte word.
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ unsigned rne16_nan(float x) {
+    const unsigned u = __float_as_uint(x);
+    const unsigned r = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+    return (u & 0x7fffffffu) > 0x7f800000u ? ((u >> 16) | 0x40u) : r;
+}
+
+__global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict__ x, int ldx, int C8, unsigned short* __restrict__ y, int ldy,
+                                                        long long total8) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total8; i += (long long)gridDim.x * blockDim.x) {
+        const long long r = i / C8;
+        const int c = (int)(i - r * C8) * 8;
+        const float* s = x + (size_t)r * ldx + c;
+        const f32x4 a = *reinterpret_cast<const f32x4*>(s), b = *reinterpret_cast<const f32x4*>(s + 4);
+        u32x4 o;
+        o.x = rne16_nan(a.x) | (rne16_nan(a.y) << 16);
+        o.y = rne16_nan(a.z) | (rne16_nan(a.w) << 16);
+        o.z = rne16_nan(b.x) | (rne16_nan(b.y) << 16);
+        o.w = rne16_nan(b.z) | (rne16_nan(b.w) << 16);
+        *reinterpret_cast<u32x4*>(y + (size_t)r * ldy + c) = o;
+    }
+}
+
 }  // namespace
 
 extern "C" int mrfa_pack_conv_weight(void* stream, const float* src, float* dst, int Cout, int Cin, int R, int S, int mode) {
@@ -229,5 +255,16 @@ extern "C" int mrfa_copy_view(void* stream, const float* x, int ldx, long long r
     hipLaunchKernelGGL(copy_view_kernel, dim3(stream_grid(rows * C, 256)), dim3(256), 0, (hipStream_t)stream, x, ldx, rows, C, y, ldy,
                        mul, accumulate);
     MRFA_CHECK_LAUNCH("copy_view");
+    return 0;
+}
+
+extern "C" int mrfa_cast_bf16(void* stream, const float* x, int ldx, long long rows, int C, unsigned short* y, int ldy) {
+    MRFA_CHECK_ARG(x && y && rows >= 0 && C > 0 && ldx >= C && ldy >= C, "cast_bf16: bad args");
+    MRFA_CHECK_ARG(C % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 && aligned16(x) && aligned16(y),
+                   "cast_bf16: needs C %% 8 == 0, ldx %% 8 == 0, ldy %% 8 == 0 and 16-byte aligned pointers (C %d, ldx %d, ldy %d)", C, ldx, ldy);
+    if (rows == 0) return 0;
+    const long long total8 = rows * (C / 8);
+    hipLaunchKernelGGL(cast_bf16_kernel, dim3(stream_grid(total8, 256)), dim3(256), 0, (hipStream_t)stream, x, ldx, C / 8, y, ldy, total8);
+    MRFA_CHECK_LAUNCH("cast_bf16");
     return 0;
 }

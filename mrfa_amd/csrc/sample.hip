@@ -117,6 +117,52 @@ __global__ __launch_bounds__(256) void grid_sample_fwd_vec_kernel(const float* _
     }
 }
 
+// bf16-input variant (the source-feature cache of the animation loop: one producer, this consumer, no backward): a lane owns EIGHT consecutive channels, so
+// each tap is still one 16-byte load but covers twice the channels; LPP = lanes per (pixel, chunk of 8 * LPP channels), LPP = 1 is the general form (any
+// C % 8 == 0: consecutive lanes take consecutive 8-channel groups).  bf16 -> fp32 is exact (a shift / a mask per pair); taps, selection and the blend are
+// grid_sample_fwd_vec_kernel's, in the same order, so the result is that kernel's on the widened input.
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ void widen8(const u32x4 r, f32x4& a, f32x4& b) {
+    a.x = __uint_as_float(r.x << 16); a.y = __uint_as_float(r.x & 0xffff0000u);
+    a.z = __uint_as_float(r.y << 16); a.w = __uint_as_float(r.y & 0xffff0000u);
+    b.x = __uint_as_float(r.z << 16); b.y = __uint_as_float(r.z & 0xffff0000u);
+    b.z = __uint_as_float(r.w << 16); b.w = __uint_as_float(r.w & 0xffff0000u);
+}
+
+template <int LPP>
+__global__ __launch_bounds__(256) void grid_sample_bf16_fwd_kernel(const unsigned short* __restrict__ in, int ldi, long long in_bstride, int in_rep,
+                                                                  int Hi, int Wi, int C, const float* __restrict__ grid, int ldg,
+                                                                  long long npix, int Ho, int Wo, float* __restrict__ out, int ldo, int mode) {
+    const int chunks = C / (8 * LPP);
+    const long long items = npix * chunks;                 // (pixel, chunk of 8*LPP channels)
+    const int sub = threadIdx.x % LPP;
+    const long long first = (blockIdx.x * (long long)blockDim.x + threadIdx.x) / LPP;
+    const long long step = ((long long)gridDim.x * blockDim.x) / LPP;
+    for (long long it = first; it < items; it += step) {
+        const long long opix = it / chunks;
+        const int c = (int)(it - opix * chunks) * 8 * LPP + sub * 8;
+        const int ox = (int)(opix % Wo);
+        const long long t = opix / Wo;
+        const int oy = (int)(t % Ho);
+        const int n = (int)(t / Ho);
+        float ix, iy;
+        sample_coords(grid, ldg, opix, ox, oy, Wi, Hi, mode, ix, iy);
+        const Taps4 tp = make_taps4(ix, iy, Wi, Hi);
+        const unsigned short* base = in + (size_t)(n / in_rep) * in_bstride + c;
+        const u32x4 r00 = *reinterpret_cast<const u32x4*>(base + tp.o00 * ldi), r01 = *reinterpret_cast<const u32x4*>(base + tp.o01 * ldi);
+        const u32x4 r10 = *reinterpret_cast<const u32x4*>(base + tp.o10 * ldi), r11 = *reinterpret_cast<const u32x4*>(base + tp.o11 * ldi);
+        f32x4 a00, b00, a01, b01, a10, b10, a11, b11;
+        widen8(r00, a00, b00); widen8(r01, a01, b01); widen8(r10, a10, b10); widen8(r11, a11, b11);
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        const f32x4 va = tp.w00 * (tp.ok00 ? a00 : z) + tp.w01 * (tp.ok01 ? a01 : z) + tp.w10 * (tp.ok10 ? a10 : z) + tp.w11 * (tp.ok11 ? a11 : z);
+        const f32x4 vb = tp.w00 * (tp.ok00 ? b00 : z) + tp.w01 * (tp.ok01 ? b01 : z) + tp.w10 * (tp.ok10 ? b10 : z) + tp.w11 * (tp.ok11 ? b11 : z);
+        float* o = out + (size_t)opix * ldo + c;
+        *reinterpret_cast<f32x4*>(o) = va;
+        *reinterpret_cast<f32x4*>(o + 4) = vb;
+    }
+}
+
 template <int LPP>
 __global__ __launch_bounds__(256) void grid_sample_bwd_vec_kernel(const float* __restrict__ in, int ldi, long long in_bstride, int in_rep,
                                                                  int Hi, int Wi, int C, const float* __restrict__ grid, int ldg,
@@ -565,6 +611,25 @@ extern "C" int mrfa_grid_sample_fwd(void* stream, const float* in, int ldi, long
     hipLaunchKernelGGL(grid_sample_fwd_kernel, dim3(stream_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, in, ldi, in_bstride,
                        in_rep, Hi, Wi, C, grid, ldg, N, Ho, Wo, out, ldo, mode, total);
     MRFA_CHECK_LAUNCH("grid_sample_fwd");
+    return 0;
+}
+
+extern "C" int mrfa_grid_sample_bf16_fwd(void* stream, const unsigned short* in, int ldi, long long in_bstride, int in_rep, int Hi, int Wi, int C,
+                                         const float* grid, int ldg, int N, int Ho, int Wo, float* out, int ldo, int mode) {
+    MRFA_CHECK_ARG(in && grid && out && C > 0 && N > 0 && in_rep >= 1 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && ldi >= C && ldo >= C && ldg >= 2 &&
+                   (mode == 0 || mode == 1), "grid_sample_bf16_fwd: bad args");
+    MRFA_CHECK_ARG(C % 8 == 0 && ldi % 8 == 0 && in_bstride % 8 == 0 && ldo % 4 == 0 && aligned16(in) && aligned16(out),
+                   "grid_sample_bf16_fwd: needs C %% 8 == 0, ldi %% 8 == 0, in_bstride %% 8 == 0, ldo %% 4 == 0 and 16-byte aligned in / out "
+                   "(C %d, ldi %d, ldo %d)", C, ldi, ldo);
+    const long long npix = (long long)N * Ho * Wo;
+    const int c8 = C / 8;
+    const int lpp = c8 % 64 == 0 ? 64 : (c8 == 32 ? 32 : (c8 == 16 ? 16 : (c8 == 8 ? 8 : 1)));
+    dim3 g(stream_grid(npix * c8, 256));
+#define GSH(L) hipLaunchKernelGGL((grid_sample_bf16_fwd_kernel<L>), g, dim3(256), 0, (hipStream_t)stream, in, ldi, in_bstride, in_rep, Hi, Wi, C, \
+                                   grid, ldg, npix, Ho, Wo, out, ldo, mode)
+    if (lpp == 64) GSH(64); else if (lpp == 32) GSH(32); else if (lpp == 16) GSH(16); else if (lpp == 8) GSH(8); else GSH(1);
+#undef GSH
+    MRFA_CHECK_LAUNCH("grid_sample_bf16_fwd");
     return 0;
 }
 

@@ -387,12 +387,14 @@ def _conv_params() -> hip.ConvParams:
 
 # ------------------------------------------------------------------------------------------------- storage / views
 class Storage:
-    """[rows, ld] fp32 buffer + lazily allocated gradient buffer of the same geometry."""
-    __slots__ = ("data", "grad", "rows", "ld", "grad_noinit", "fresh", "bwd_masked", "bn_hint", "seq", "plan")
+    """[rows, ld] fp32 buffer + lazily allocated gradient buffer of the same geometry.  A bf16 buffer (Ctx.to_bf16: inference caches) has the same
+    geometry, counted in bf16 elements, and never a gradient buffer."""
+    __slots__ = ("data", "dtype", "grad", "rows", "ld", "grad_noinit", "fresh", "bwd_masked", "bn_hint", "seq", "plan")
 
     def __init__(self, data: torch.Tensor):
-        assert data.dim() == 2 and data.dtype == torch.float32 and data.is_contiguous()
+        assert data.dim() == 2 and data.dtype in (torch.float32, torch.bfloat16) and data.is_contiguous()
         self.data = data
+        self.dtype = data.dtype
         self.rows, self.ld = data.shape
         self.grad: Optional[torch.Tensor] = None
         # True: the gradient buffer has exactly one writer that overwrites all of it (a raw conv output whose only consumer
@@ -416,6 +418,8 @@ class Storage:
         self.plan = None
 
     def grad_buf(self) -> torch.Tensor:
+        if self.dtype != torch.float32:
+            raise TypeError("a bf16 storage has no gradient buffer (bf16 activations are inference caches)")
         if self.grad is None:
             self.grad = torch.zeros_like(self.data)
         elif self.fresh:
@@ -446,8 +450,22 @@ class View:
         return self.st.ld
 
     @property
+    def dtype(self) -> torch.dtype:
+        return self.st.dtype
+
+    @property
     def ptr(self) -> int:
+        """fp32 data pointer: what every fp32 kernel is handed.  The ONE place that keeps a bf16 view away from them."""
+        if self.st.dtype != torch.float32:
+            raise TypeError(f"a {self.st.dtype} view was handed to an fp32 kernel (View.ptr): only Ctx.grid_sample reads bf16 views (View.ptr16)")
         return self.st.data.data_ptr() + 4 * self.coff
+
+    @property
+    def ptr16(self) -> int:
+        """bf16 data pointer (mrfa_cast_bf16's destination, mrfa_grid_sample_bf16_fwd's input)"""
+        if self.st.dtype != torch.bfloat16:
+            raise TypeError(f"View.ptr16 of a {self.st.dtype} view")
+        return self.st.data.data_ptr() + 2 * self.coff
 
     @property
     def gptr(self) -> int:
@@ -1028,6 +1046,15 @@ class Ctx:
         t = torch.empty((v.N, v.C, v.H, v.W), dtype=torch.float32, device=self.dev)
         self._chk(self.L.mrfa_nhwc_to_nchw(self.s, v.ptr, v.ld, t.data_ptr(), v.N, v.C, v.H, v.W, 0), "nhwc_to_nchw")
         return t
+
+    def to_bf16(self, v: View) -> View:
+        """bf16 copy (round to nearest even) of an fp32 view with C % 8 == 0, ld == C.  Inference only: a bf16 view has no backward and only
+        grid_sample reads one."""
+        if self.record:
+            raise RuntimeError("Ctx.to_bf16: bf16 activations are inference caches, not legal in a recording (training) program")
+        out = View(Storage(torch.empty((v.rows, v.C), dtype=torch.bfloat16, device=self.dev)), v.N, v.H, v.W, v.C)
+        self._chk(self.L.mrfa_cast_bf16(self.s, v.ptr, v.ld, v.rows, v.C, out.ptr16, out.ld), "cast_bf16")
+        return out
 
     def grad_to_nchw(self, v: View) -> torch.Tensor:
         t = torch.empty((v.N, v.C, v.H, v.W), dtype=torch.float32, device=self.dev)
@@ -1677,6 +1704,12 @@ class Ctx:
         assert grid.C == 2 and n_out == inp.N * in_rep
         out = out or self.new(n_out, grid.H, grid.W, inp.C)
         bs = inp.H * inp.W * inp.ld
+        if inp.dtype == torch.bfloat16:                  # a bf16 cache (to_bf16): forward only, fp32 grid and output
+            if self.record:
+                raise RuntimeError("Ctx.grid_sample: a bf16 input has no backward, not legal in a recording (training) program")
+            self._chk(self.L.mrfa_grid_sample_bf16_fwd(self.s, inp.ptr16, inp.ld, bs, in_rep, inp.H, inp.W, inp.C, grid.ptr, grid.ld, n_out,
+                                                       grid.H, grid.W, out.ptr, out.ld, mode), "grid_sample_bf16_fwd")
+            return out
         self._chk(self.L.mrfa_grid_sample_fwd(self.s, inp.ptr, inp.ld, bs, in_rep, inp.H, inp.W, inp.C, grid.ptr, grid.ld, n_out,
                                               grid.H, grid.W, out.ptr, out.ld, mode), "grid_sample_fwd")
         if self.record:

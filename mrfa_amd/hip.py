@@ -159,6 +159,7 @@ _SIGNATURES = {
     "mrfa_bn_act_fwd": ([_V, C.POINTER(BnActParams)], C.c_int),
     "mrfa_bn_act_bwd": ([_V, C.POINTER(BnBwdParams)], C.c_int),
     "mrfa_grid_sample_fwd": ([_V, _V, _I, _L, _I, _I, _I, _I, _V, _I, _I, _I, _I, _V, _I, _I], C.c_int),
+    "mrfa_grid_sample_bf16_fwd": ([_V, _V, _I, _L, _I, _I, _I, _I, _V, _I, _I, _I, _I, _V, _I, _I], C.c_int),
     "mrfa_grid_sample_bwd": ([_V, _V, _I, _L, _I, _I, _I, _I, _V, _I, _I, _I, _I, _V, _I, _I, _V, _I, _L, _V, _I], C.c_int),
     "mrfa_resize_bilinear_fwd": ([_V, _V, _I, _I, _I, _I, _I, _V, _I, _I, _I, _F, _I], C.c_int),
     "mrfa_resize_bilinear_bwd": ([_V, _V, _I, _I, _I, _I, _I, _V, _I, _I, _I, _F], C.c_int),
@@ -174,6 +175,7 @@ _SIGNATURES = {
     "mrfa_bias_act": ([_V, _V, _I, _L, _I, _V, _I, _V, _I, _V], C.c_int),
     "mrfa_act_bwd": ([_V, _V, _I, _V, _I, _L, _I, _I, _V, _I, _I], C.c_int),
     "mrfa_copy_view": ([_V, _V, _I, _L, _I, _V, _I, _F, _I], C.c_int),
+    "mrfa_cast_bf16": ([_V, _V, _I, _L, _I, _V, _I], C.c_int),
     "mrfa_timestamp": ([_V, _V], C.c_int),
     "mrfa_conv2d_bwdstats_supported": ([C.POINTER(ConvParams)], C.c_int),
     "mrfa_conv2d_groups_supported": ([C.POINTER(ConvParams)], C.c_int),
@@ -219,7 +221,7 @@ _SIGNATURES = {
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 LN_SLOTS = 16          # MRFA_LN_SLOTS
 RESIZE_SUM_TERMS = 4   # MRFA_RESIZE_SUM_TERMS
-ABI_VERSION = 9        # MRFA_ABI_VERSION of include/mrfa_hip.h: the struct layouts above mirror THAT header; lib() refuses any other library
+ABI_VERSION = 10       # MRFA_ABI_VERSION of include/mrfa_hip.h: the struct layouts above mirror THAT header; lib() refuses any other library
 
 _lib = None
 

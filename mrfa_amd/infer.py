@@ -10,11 +10,20 @@ import torch
 from torch import nn
 
 
+def _check_cache_dtype(cache_dtype):
+    if cache_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"cache_dtype must be torch.float32 or torch.bfloat16, not {cache_dtype}")
+    return cache_dtype
+
+
 class Animator:
-    def __init__(self, model: nn.Module, graph: bool = False):
-        """model: mrfa_amd.train.HotPath or mrfa_amd.modules.model.MRFA (attributes encoder / dense_motion / decoder / down)"""
+    def __init__(self, model: nn.Module, graph: bool = False, cache_dtype: torch.dtype = torch.float32):
+        """model: mrfa_amd.train.HotPath or mrfa_amd.modules.model.MRFA (attributes encoder / dense_motion / decoder / down).
+        cache_dtype: storage of the cached source feature pyramid (RaftFlow.encode_source(feature_dtype=)); torch.bfloat16 halves what the cache holds
+        and what the per-frame warps gather, at the cost of one rounding of the source features"""
         self.m = model.eval()
         self.use_graph = graph
+        self.cache_dtype = _check_cache_dtype(cache_dtype)
         self.source = None
         self._g: Optional[torch.cuda.CUDAGraph] = None
 
@@ -24,7 +33,7 @@ class Animator:
         self.source = source
         self.kp_s = m.encoder(source)
         self.img_down = m.down(source)
-        self.cache = m.decoder.encode_source(self.kp_s["kp"], self.img_down, source)
+        self.cache = m.decoder.encode_source(self.kp_s["kp"], self.img_down, source, feature_dtype=self.cache_dtype)
         self._g = None
 
     @torch.no_grad()
@@ -112,11 +121,11 @@ def psnr(img1: torch.Tensor, img2: torch.Tensor):
 
 
 @torch.no_grad()
-def reconstruction(model: nn.Module, video: torch.Tensor, graph: bool = False):
+def reconstruction(model: nn.Module, video: torch.Tensor, graph: bool = False, cache_dtype: torch.dtype = torch.float32):
     """The reference's reconstruction loop (reconstruction.py:52-70) on one clip: source = frame 0, driving = every frame t,
     metrics mean|out - driving| and PSNR per frame.  video: (B,3,T,H,W) in [0,1].  The source is fixed for the whole clip, so
     the source half of the path is computed once (Animator).  Returns {'prediction': (B,3,T,H,W), 'l1': [T], 'psnr': [T]}."""
-    anim = Animator(model, graph=graph)
+    anim = Animator(model, graph=graph, cache_dtype=cache_dtype)
     anim.set_source(video[:, :, 0].contiguous())
     preds, l1, ps = [], [], []
     for t in range(video.shape[2]):
@@ -130,13 +139,14 @@ def reconstruction(model: nn.Module, video: torch.Tensor, graph: bool = False):
 
 @torch.no_grad()
 def make_animation(model: nn.Module, source: torch.Tensor, driving_video: torch.Tensor, relative: bool = True,
-                   adapt_movement_scale: bool = False, graph: bool = False):
+                   adapt_movement_scale: bool = False, graph: bool = False, cache_dtype: torch.dtype = torch.float32):
     """demo.py:47-73 / animate_ddp.py:88-105: animate ONE source by the motion of a driving clip (B,3,T,H,W); with
     relative=True the driving keypoints go through normalize_kp against the first driving frame.  Returns (B,3,T,H,W)."""
+    _check_cache_dtype(cache_dtype)
     m = model.eval()
     kp_s = m.encoder(source)
     img_down = m.down(source)
-    cache = m.decoder.encode_source(kp_s["kp"], img_down, source)
+    cache = m.decoder.encode_source(kp_s["kp"], img_down, source, feature_dtype=cache_dtype)
     kp_init = m.encoder(driving_video[:, :, 0].contiguous())
     outs = []
     for t in range(driving_video.shape[2]):

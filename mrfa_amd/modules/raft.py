@@ -219,16 +219,24 @@ class RaftFlow(nn.Module):
             maps = [F.interpolate(o.tensor().permute(0, 3, 1, 2), size=self.size, mode='bilinear', align_corners=True) for o in occs]
             return torch.cat(maps, dim=3)
 
-    def encode_source(self, kp_s, img, img_full):
+    def encode_source(self, kp_s, img, img_full, feature_dtype=torch.float32):
         """Source-only half of the forward (inference): the generator's 6-level feature pyramid of the source image and
         the source structure keys k_s / pooled k_s (raft.py:143,179,181) -- ~38 GF per frame that an animation loop over
-        ONE source re-computes for every driving frame (demo.py:47-73).  Returns an opaque cache for forward(source_cache=)."""
+        ONE source re-computes for every driving frame (demo.py:47-73).  Returns an opaque cache for forward(source_cache=).
+        feature_dtype=torch.bfloat16 (extension): the pyramid levels with C % 8 == 0 are kept as bf16 (rounded to nearest even once, here) and their
+        fp32 tensors released -- half the bytes held and half the bytes every warp of every frame gathers; the warps widen them exactly and blend in
+        fp32.  The source image (a warp of it is an output) and k_s / pooled k_s stay fp32."""
         assert not self.training, "source caching is an inference feature (eval-mode BatchNorm)"
+        if feature_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"feature_dtype must be torch.float32 or torch.bfloat16, not {feature_dtype}")
         with torch.no_grad():
             e = Ctx(img_full.device, train=False, record=False)
             gen = self.generator
             imgf = e.from_nchw(img_full)
-            cache = {"imgf": imgf, "feature": gen.run_encode(e, imgf), "shape": tuple(img_full.shape)}
+            feature = gen.run_encode(e, imgf)
+            if feature_dtype == torch.bfloat16:          # (a level the bf16 warp cannot take stays fp32)
+                feature = [e.to_bf16(f) if f.C % 8 == 0 and f.ld % 8 == 0 and f.coff % 4 == 0 else f for f in feature]
+            cache = {"imgf": imgf, "feature": feature, "shape": tuple(img_full.shape), "dtype": feature_dtype}
             if not self.prior_only:
                 h, w = img.shape[2], img.shape[3]
                 in_s = self._source_input(e, kp_s, img, h, w)
