@@ -357,7 +357,11 @@ int mrfa_bn_param_grad_groups(void* stream, const double* red, int C, int groups
  * mode 1: grid = flow (dx,dy) in pixels; sample at (x+dx, y+dy), align_corners=True semantics
  *         (bilinear_sampler(img, flow+coords_grid), util.py:26-38; raft.py:247,260,302)
  * grid is (N,Ho,Wo,2) fp32 with leading dimension ldg.  Output image n samples input image n / in_rep (in_rep = 11
- * for DenseMotion's repeated source, dense_motion.py:80-81, else 1); in_bstride = floats between input images.     */
+ * for DenseMotion's repeated source, dense_motion.py:80-81, else 1); in_bstride = floats between input images.
+ * A sample whose pixel coordinate is NaN, +-inf, <= -1 or >= Wi (Hi) contributes nothing anywhere (out = 0, nothing added to din or dgrid), a tap outside
+ * the image counts as 0 in the output and in the difference quotients of dgrid, and at an exact integer coordinate dgrid is the one-sided derivative
+ * of the cell [x0, x0 + 1), x0 = floor(ix); the correlation lookup below samples by the same rule.  mode other than 0 / 1, a non-positive size or a
+ * leading dimension below the channel count is an argument error.                                                   */
 int mrfa_grid_sample_fwd(void* stream, const float* in, int ldi, long long in_bstride, int in_rep, int Hi, int Wi, int C,
                          const float* grid, int ldg, int N, int Ho, int Wo, float* out, int ldo, int mode);
 int mrfa_grid_sample_bwd(void* stream, const float* in, int ldi, long long in_bstride, int in_rep, int Hi, int Wi, int C,

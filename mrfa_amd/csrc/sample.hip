@@ -595,7 +595,9 @@ extern "C" int mrfa_warp_frame_reflect(void* stream, const float* in, int N, int
 
 extern "C" int mrfa_grid_sample_fwd(void* stream, const float* in, int ldi, long long in_bstride, int in_rep, int Hi, int Wi, int C,
                                     const float* grid, int ldg, int N, int Ho, int Wo, float* out, int ldo, int mode) {
-    MRFA_CHECK_ARG(in && grid && out && C > 0 && N > 0 && in_rep >= 1, "grid_sample_fwd: bad args");
+    MRFA_CHECK_ARG(in && grid && out && C > 0 && N > 0 && in_rep >= 1 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && ldi >= C && ldo >= C && ldg >= 2 &&
+                   (mode == 0 || mode == 1), "grid_sample_fwd: bad args (sizes must be positive, ldi >= C, ldo >= C, ldg >= 2, mode 0 or 1; C %d, ldi %d, "
+                   "ldo %d, ldg %d, mode %d)", C, ldi, ldo, ldg, mode);
     const long long total = (long long)N * Ho * Wo * C;
     const int lpp = C % 256 == 0 ? 64 : (C == 128 ? 32 : (C == 64 ? 16 : 0));
     if (lpp && ldi % 4 == 0 && ldo % 4 == 0 && in_bstride % 4 == 0 && aligned16(in) && aligned16(out)) {
@@ -636,7 +638,10 @@ extern "C" int mrfa_grid_sample_bf16_fwd(void* stream, const unsigned short* in,
 extern "C" int mrfa_grid_sample_bwd(void* stream, const float* in, int ldi, long long in_bstride, int in_rep, int Hi, int Wi, int C,
                                     const float* grid, int ldg, int N, int Ho, int Wo, const float* dout, int lddo, int mode,
                                     float* din, int lddi, long long din_bstride, float* dgrid, int lddg) {
-    MRFA_CHECK_ARG(in && grid && dout && C > 0 && N > 0 && in_rep >= 1, "grid_sample_bwd: bad args");
+    MRFA_CHECK_ARG(in && grid && dout && C > 0 && N > 0 && in_rep >= 1 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && ldi >= C && lddo >= C && ldg >= 2 &&
+                   (!din || lddi >= C) && (!dgrid || lddg >= 2) && (mode == 0 || mode == 1),
+                   "grid_sample_bwd: bad args (sizes must be positive, ldi >= C, lddo >= C, ldg >= 2, lddi >= C with din, lddg >= 2 with dgrid, mode 0 or 1; "
+                   "C %d, ldi %d, lddo %d, ldg %d, lddi %d, lddg %d, mode %d)", C, ldi, lddo, ldg, lddi, lddg, mode);
     const long long npix = (long long)N * Ho * Wo;
     const int lpp = C % 256 == 0 ? 64 : (C == 128 ? 32 : (C == 64 ? 16 : 0));
     if (lpp && !din && ldi % 4 == 0 && lddo % 4 == 0 && in_bstride % 4 == 0 && aligned16(in) && aligned16(dout)) {
@@ -659,7 +664,8 @@ extern "C" int mrfa_grid_sample_bwd(void* stream, const float* in, int ldi, long
 
 extern "C" int mrfa_resize_bilinear_fwd(void* stream, const float* in, int ldi, int N, int Hi, int Wi, int C, float* out, int ldo,
                                         int Ho, int Wo, float scale_mul, int accumulate) {
-    MRFA_CHECK_ARG(in && out && C > 0 && N > 0, "resize_fwd: bad args");
+    MRFA_CHECK_ARG(in && out && C > 0 && N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && ldi >= C && ldo >= C,
+                   "resize_fwd: bad args (sizes must be positive, ldi >= C, ldo >= C; C %d, ldi %d, ldo %d, %d x %d -> %d x %d)", C, ldi, ldo, Hi, Wi, Ho, Wo);
     const long long total = (long long)N * Ho * Wo * C;
     hipLaunchKernelGGL(resize_fwd_kernel, dim3(stream_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, in, ldi, N, Hi, Wi, C, out, ldo,
                        Ho, Wo, scale_mul, accumulate, total);
@@ -669,7 +675,8 @@ extern "C" int mrfa_resize_bilinear_fwd(void* stream, const float* in, int ldi, 
 
 extern "C" int mrfa_resize_bilinear_bwd(void* stream, const float* dout, int lddo, int N, int Hi, int Wi, int C, float* din, int lddi,
                                         int Ho, int Wo, float scale_mul) {
-    MRFA_CHECK_ARG(dout && din && C > 0 && N > 0, "resize_bwd: bad args");
+    MRFA_CHECK_ARG(dout && din && C > 0 && N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && lddo >= C && lddi >= C,
+                   "resize_bwd: bad args (sizes must be positive, lddo >= C, lddi >= C; C %d, lddo %d, lddi %d, %d x %d -> %d x %d)", C, lddo, lddi, Hi, Wi, Ho, Wo);
     if (Ho >= Hi && Wo >= Wi) {
         const long long total_in = (long long)N * Hi * Wi * C;
         hipLaunchKernelGGL(resize_bwd_gather_kernel, dim3(stream_grid(total_in, 256)), dim3(256), 0, (hipStream_t)stream, dout, lddo, N, Hi,
@@ -721,8 +728,9 @@ extern "C" int mrfa_resize_sum_multi_bwd(void* stream, const mrfa_resize_sum_des
 
 extern "C" int mrfa_corr_lookup_fwd(void* stream, const float* vol0, const float* vol1, int Hs, int Ws, const float* coords, int ldc,
                                     long long Q, int radius, float* out, int ldo) {
-    MRFA_CHECK_ARG(vol0 && vol1 && coords && out && Q > 0, "corr_lookup_fwd: bad args");
-    MRFA_CHECK_ARG((2 * radius + 1) * (2 * radius + 1) <= 64, "corr_lookup: window must fit one wave (radius <= 3)");
+    MRFA_CHECK_ARG(radius >= 0 && radius <= 3, "corr_lookup: window must fit one wave (0 <= radius <= 3, got %d)", radius);
+    MRFA_CHECK_ARG(vol0 && vol1 && coords && out && Q > 0 && Hs >= 2 && Ws >= 2 && ldc >= 2 && ldo >= 2 * (2 * radius + 1) * (2 * radius + 1),
+                   "corr_lookup_fwd: bad args (Hs, Ws >= 2, ldc >= 2, ldo >= 2 (2r+1)^2; Hs %d, Ws %d, ldc %d, ldo %d, radius %d)", Hs, Ws, ldc, ldo, radius);
     hipLaunchKernelGGL((corr_lookup_kernel<false>), dim3(stream_grid(Q * 64, 256)), dim3(256), 0, (hipStream_t)stream, vol0, vol1, Hs, Ws,
                        coords, ldc, Q, radius, out, ldo, nullptr, 0, nullptr, nullptr, nullptr, 0);
     MRFA_CHECK_LAUNCH("corr_lookup_fwd");
@@ -732,9 +740,11 @@ extern "C" int mrfa_corr_lookup_fwd(void* stream, const float* vol0, const float
 extern "C" int mrfa_corr_lookup_bwd(void* stream, const float* vol0, const float* vol1, int Hs, int Ws, const float* coords, int ldc,
                                     long long Q, int radius, const float* dout, int lddo, float* dvol0, float* dvol1, float* dcoords,
                                     int lddc) {
-    MRFA_CHECK_ARG(vol0 && vol1 && coords && dout && Q > 0, "corr_lookup_bwd: bad args");
+    MRFA_CHECK_ARG(radius >= 0 && radius <= 3, "corr_lookup: window must fit one wave (0 <= radius <= 3, got %d)", radius);
+    MRFA_CHECK_ARG(vol0 && vol1 && coords && dout && Q > 0 && Hs >= 2 && Ws >= 2 && ldc >= 2 && lddo >= 2 * (2 * radius + 1) * (2 * radius + 1) &&
+                   (!dcoords || lddc >= 2), "corr_lookup_bwd: bad args (Hs, Ws >= 2, ldc >= 2, lddo >= 2 (2r+1)^2, lddc >= 2 with dcoords; Hs %d, Ws %d, "
+                   "ldc %d, lddo %d, lddc %d, radius %d)", Hs, Ws, ldc, lddo, lddc, radius);
     MRFA_CHECK_ARG((dvol0 == nullptr) == (dvol1 == nullptr), "corr_lookup_bwd: dvol0/dvol1 must both be given or both null");
-    MRFA_CHECK_ARG((2 * radius + 1) * (2 * radius + 1) <= 64, "corr_lookup: window must fit one wave (radius <= 3)");
     hipLaunchKernelGGL((corr_lookup_kernel<true>), dim3(stream_grid(Q * 64, 256)), dim3(256), 0, (hipStream_t)stream, vol0, vol1, Hs, Ws,
                        coords, ldc, Q, radius, nullptr, 0, dout, lddo, dvol0, dvol1, dcoords, lddc);
     MRFA_CHECK_LAUNCH("corr_lookup_bwd");

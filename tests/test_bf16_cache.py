@@ -18,6 +18,7 @@ from mrfa_amd.modules import RaftFlow
 from oracle import mrfa_oracle as O
 from tests import cases
 from tests.emu_bf16 import cache_pyramid_bytes, cache_pyramid_nchw, emulated_hip_bf16, oracle_pyramid
+from tests.sample_grids import gs_grid as _gs_grid
 from tests.test_oracle_golden import raft_inputs
 
 DEV = "cuda:0"
@@ -211,37 +212,6 @@ def test_cast_bf16_is_bit_identical_round_to_nearest_even():
     assert torch.isnan(xn[:, 3]).all()
     got = _cast(xn.to(DEV), 8).cpu()
     assert torch.isnan(got[:, 3]).all() and (got.float()[:, [0, 1, 2, 4, 5, 6, 7]] == 1).all()
-
-
-def _gs_grid(N, Ho, Wo, Hi, Wi, mode, seed):
-    """sampling grid with ordinary, integer, border, far-outside and NaN coordinates; returns (grid [N*Ho*Wo, 2], rows wholly outside)"""
-    g = torch.Generator().manual_seed(seed)
-    n = N * Ho * Wo
-    if mode == 0:
-        grid = torch.rand(n, 2, generator=g) * 2.6 - 1.3
-        px = lambda ix, iy: torch.tensor([(2 * ix + 1) / Wi - 1, (2 * iy + 1) / Hi - 1])          # pixel coordinate -> normalised, align_corners=False
-        def put(i, ix, iy):
-            grid[i] = px(ix, iy)
-    else:
-        grid = torch.rand(n, 2, generator=g) * 10 - 5
-        def put(i, ix, iy):
-            ox, oy = i % Wo, (i // Wo) % Ho
-            grid[i] = torch.tensor([ix - ox, iy - oy], dtype=torch.float32)
-    special = [(2.0, 3.0), (0.0, 0.0), (Wi - 1.0, Hi - 1.0), (-0.5, 2.0), (-1.0, 1.0), (Wi - 0.5, 1.25), (float(Wi), 2.0), (1.5, -0.25), (3.0, -1.0),
-               (2.5, Hi - 0.75), (1.0, float(Hi)), (-0.999, -0.999), (Wi - 1.0, 0.0)]
-    outside = [(-7.0, 2.0), (1e6, 1e6), (-1e30, 3.0), (2.0, Hi + 40.0), (float("nan"), 1.0), (1.0, float("nan")), (float("nan"), float("nan")),
-               (float("inf"), 0.0), (-1.5, -1.5)]
-    for i, (ix, iy) in enumerate(special):
-        put(3 + 2 * i, ix, iy)
-    rows = []
-    for i, (ix, iy) in enumerate(outside):
-        r = 4 + 2 * len(special) + 2 * i
-        if np.isfinite(ix) and np.isfinite(iy):
-            put(r, ix, iy)
-        else:
-            grid[r] = torch.tensor([ix, iy])                                  # NaN / infinite grid values themselves
-        rows.append(r)
-    return grid, rows
 
 
 def _tap_max(xw, grid, N, in_rep, Hi, Wi, Ho, Wo, mode):
