@@ -2,6 +2,7 @@
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only build container; the resulting .so travels to the
 GPU box with the repo snapshot (it is git-ignored, not gpurun-ignored)."""
+import glob
 import os
 import subprocess
 import sys
@@ -26,7 +27,7 @@ def _stale(out, deps):
 def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(LIBDIR, exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    headers = [os.path.join(ROOT, "include", "mrfa_hip.h"), os.path.join(CSRC, "common.h")]
+    headers = [os.path.join(ROOT, "include", "mrfa_hip.h")] + sorted(glob.glob(os.path.join(CSRC, "*.h")))
     objs = []
     procs = []
     for src in SOURCES:

@@ -125,6 +125,13 @@ static inline int stream_grid(long long work_items, int block) {
     return (int)g;
 }
 
+// XCD-aware tile order: workgroup b runs on XCD b % 8 (each XCD has a private 4 MiB L2).  Give every XCD one contiguous band of output tiles so
+// the 3x3 halo rows and the tile's Cout-siblings are re-read from ITS L2 instead of being fetched by all eight.  (gridDim.x is a multiple of 8.)
+__device__ __forceinline__ int xcd_tile_index() {
+    const int per_xcd = (int)gridDim.x >> 3;
+    return (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);
+}
+
 // Kernels of the latency-bound chains (the keypoint encoder's ~3 500 small launches per step) raise their wave priority: in the training step they run
 // BESIDE chip-filling matrix kernels (the deferred weight gradients, one 256-VGPR workgroup per CU for hundreds of microseconds), and a chain kernel's few
 // instructions otherwise take turns with that workgroup's on the same SIMD.  s_setprio only reorders instruction issue between co-resident waves.

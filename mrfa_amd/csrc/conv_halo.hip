@@ -1,4 +1,4 @@
-// 3x3 "same" convolution on the bf16 matrix pipe with exactly split fp32 operands (the arithmetic of conv_split.hip), tiled over
+// 3x3 "same" convolution on the bf16 matrix pipe with exactly split fp32 operands (mfma_bf16.h; conv_split.hip explains the split), tiled over
 // 2-D PATCHES of the output so that an input pixel is loaded, run through the fused prologue and split into its three bf16
 // pieces ONCE per 16-channel chunk -- not once per tap as in the row-tiled implicit GEMM of conv_split.hip.
 //
@@ -17,18 +17,14 @@
 //   * LDS images are half-planes [k 0..7 | k 8..15][pixel or row][16 B]: the 16 lanes of a ds_read_b128 lane group read 16
 //     consecutive-mod-16 pixels -> 16 distinct 16-byte bank slots, no swizzle, tap offsets stay additive.
 // Per tap and wave: 12 ds_read_b128 + 24 MFMA + ~1.5 weight loads / stores + ~10 amortised halo instructions.
-// Epilogue = conv_split.hip's (bias, eval-BN affine, residual, ReLU, accumulate, train-BN statistics).
+// Epilogue = conv_split.hip's transposed one (bias, eval-BN affine, residual, ReLU, accumulate, train-BN statistics).
 // Used for the stride-1 3x3 layers with Wout % 32 == 0 and enough patches to fill the chip; everything else stays on
 // conv_split.hip / conv_mfma.hip.  Also runs the data gradient (same conv, flipped / transposed pack).
 #include <stdlib.h>
 #include <type_traits>
-#include "common.h"
+#include "mfma_bf16.h"
 
 namespace {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int PW = 32;                             // patch width = the 32 rows of one MFMA tile
 constexpr int HP = PW + 2;                         // halo row pitch (pixels)
@@ -39,16 +35,6 @@ struct GeoB {
     static constexpr int BPLANE = 2 * BHALF;
     static constexpr int BSLAB = 3 * BPLANE;
 };
-
-// plain bf16 operands (NP = 1): round-to-nearest-even of the fp32 value, one product -- the arithmetic of a bf16 autocast
-__device__ __forceinline__ unsigned rne16(float x) {
-    const unsigned u = __float_as_uint(x);
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-__device__ __forceinline__ void round1(const f32x4 v, u32x2& p1) {
-    p1[0] = rne16(v.x) | (rne16(v.y) << 16);
-    p1[1] = rne16(v.z) | (rne16(v.w) << 16);
-}
 
 template <int PR>
 struct Geo {
@@ -61,23 +47,6 @@ struct Geo {
     static_assert(AHALF % 128 == 64, "half-plane stride must put the k 8..15 half into the other bank half");
     static_assert(NU <= 4, "halo units are loaded at taps 0,2,4,6 and stored two taps later");
 };
-
-__device__ __forceinline__ unsigned pack_hi16(float a, float b) {      // (bf16 chop of b) << 16 | (bf16 chop of a)
-    return __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u);
-}
-__device__ __forceinline__ float chop_rest(float x) { return x - __uint_as_float(__float_as_uint(x) & 0xffff0000u); }
-
-__device__ __forceinline__ void split3(const f32x4 v, u32x2& p1, u32x2& p2, u32x2& p3) {
-    const float x[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const float a = x[2 * q], b = x[2 * q + 1];
-        p1[q] = pack_hi16(a, b);
-        const float ra = chop_rest(a), rb = chop_rest(b);
-        p2[q] = pack_hi16(ra, rb);
-        p3[q] = pack_hi16(chop_rest(ra), chop_rest(rb));
-    }
-}
 
 // PH: "phase" form of a fused nearest-x2 upsample (UpBlock2d, util.py:172-176): blockIdx.y = output phase (py, px); the patch lives on the
 // LOW-resolution input grid, every output pixel (2y + py, 2x + px) reads the 2x2 source pixels {y - 1 + py, y + py} x {x - 1 + px, x + px}
@@ -104,8 +73,7 @@ __global__ __launch_bounds__(PR * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     const int lane = tid & 63;
     const int wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    const int per_xcd = (int)gridDim.x >> 3;
-    const int lin = (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);      // an XCD's L2 sees a contiguous run of patches
+    const int lin = xcd_tile_index();              // an XCD's L2 sees a contiguous run of patches
     if (lin >= total_tiles) return;
     const int tile_n = lin % tiles_n;
     int t_ = lin / tiles_n;
@@ -190,7 +158,7 @@ __global__ __launch_bounds__(PR * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
         const f32x4 z = {0.f, 0.f, 0.f, 0.f};
         v = a_inb[j] ? v : z;
         u32x2 p1, p2, p3;
-        if constexpr (NP == 1) round1(v, p1); else split3(v, p1, p2, p3);
+        bf16_pieces<NP>(v, p1, p2, p3);
         if (a_val[j]) {
             unsigned char* dst = smA + buf * G::ABUF + a_loff[j];
             *reinterpret_cast<u32x2*>(dst) = p1;
@@ -234,8 +202,6 @@ __global__ __launch_bounds__(PR * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #pragma unroll
             for (int pc = 0; pc < NPC; ++pc) a[pc][i] = *reinterpret_cast<const bf16x8*>(A + pc * G::APLANE + ((i + r) * HP + s) * 16);
         // six products, smallest first; the accumulators interleave so no MFMA waits for its predecessor
-        constexpr int PA[6] = {2, 0, 1, 1, 0, 0};
-        constexpr int PB[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
         for (int j0 = 0; j0 < TN; j0 += JG) {
             bf16x8 b[NPC][JG];
@@ -413,29 +379,9 @@ __global__ __launch_bounds__(PR * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             }
         }
         if (p.stats) {
-            // per-channel sums over the 32 pixel lanes of a half: butterfly reduce-scatter (16 + 16 shuffles for the 16 + 16 values);
-            // after it lane L holds channel index kk = 8 b4 + 4 b3 + 2 b2 + b1 (bN = bit N of L), lanes L and L ^ 1 the same total
-            auto stage = [&](float (&v)[16], auto W) {          // lanes L / L ^ 2W: the low one keeps v[0..W), the high one v[W..2W)
-                constexpr int w = decltype(W)::value;
-                const bool hi = (lane & (2 * w)) != 0;
-#pragma unroll
-                for (int k = 0; k < w; ++k) {
-                    const float send = hi ? v[k] : v[k + w];
-                    const float keep = hi ? v[k + w] : v[k];
-                    v[k] = keep + __shfl_xor(send, 2 * w, 64);
-                }
-            };
-            auto reduce16 = [&](float (&v)[16]) {
-                stage(v, std::integral_constant<int, 8>{});
-                stage(v, std::integral_constant<int, 4>{});
-                stage(v, std::integral_constant<int, 2>{});
-                stage(v, std::integral_constant<int, 1>{});
-                v[0] += __shfl_xor(v[0], 1, 64);
-            };
-            reduce16(s1);
-            reduce16(s2);
-            const int kk = ((lane >> 4) & 1) * 8 + ((lane >> 3) & 1) * 4 + ((lane >> 2) & 1) * 2 + ((lane >> 1) & 1);
-            const int cch = cb + 8 * (kk >> 2) + (kk & 3);
+            reduce_scatter16(s1, lane);
+            reduce_scatter16(s2, lane);
+            const int cch = reduce_scatter16_channel(cb, lane);
             if ((lane & 1) == 0 && cch < p.Cout) {
                 double* st = stat_slot(p, stat_group(p, (long long)n_img * p.Hout * p.Wout, (long long)p.N * p.Hout * p.Wout), blockIdx.x);   // (a patch lies in one image)
                 atomicAdd(st + cch, (double)s1[0]);

@@ -7,7 +7,7 @@
 //   * the patch's input HALO over ALL input channels is loaded once (every global load of the workgroup is issued before anything else),
 //     run through the optional BatchNorm-apply + ReLU prologue (in_scale / in_shift: the bn_act launch between the two convolutions of a
 //     residual block disappears), split exactly into its three bf16 pieces and stored in LDS -- once per workgroup, not once per tap and wave;
-//   * the arithmetic is conv_halo.hip's: six v_mfma_f32_32x32x16_bf16 products per k16 step on exactly split fp32 operands (2 500 / 6 = 417 TF/s
+//   * the arithmetic is mfma_bf16.h's: six v_mfma_f32_32x32x16_bf16 products per k16 step on exactly split fp32 operands (2 500 / 6 = 417 TF/s
 //     pipe instead of the 157 TF/s fp32 pipe); the three 2^-16-class products accumulate in their own register tile (two independent MFMA
 //     chains per output tile, and the small terms are summed among themselves before they meet the large ones);
 //   * weight fragments come STRAIGHT FROM GLOBAL MEMORY: the pre-split planes of pack modes 8 / 9 are k16-chunk-major, so the fragment of a
@@ -22,22 +22,9 @@
 // the launch's last workgroup, first phase of a BatchNorm backward in data-gradient launches: bst_*), with conv_halo.hip's 16-byte stores.
 #include <stdlib.h>
 #include <type_traits>
-#include "common.h"
+#include "mfma_bf16.h"
 
 namespace {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned lean_rne16(float x) {
-    const unsigned u = __float_as_uint(x);
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-__device__ __forceinline__ unsigned lean_pack_hi16(float a, float b) {      // (bf16 chop of b) << 16 | (bf16 chop of a)
-    return __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u);
-}
-__device__ __forceinline__ float lean_chop_rest(float x) { return x - __uint_as_float(__float_as_uint(x) & 0xffff0000u); }
 
 // The part of the small-problem kernels behind their k-loops: the two accumulator chains of a tile are added, the input-channel slices of a tile meet in LDS
 // (fixed order: bit-identical run to run), then bias / affine / residual / ReLU / accumulate, 16-byte stores, the train-mode statistics (or the first phase of a
@@ -138,32 +125,13 @@ __device__ __forceinline__ void lean_finish(const mrfa_conv_params& p, f32x16 (&
     }
     if (p.stats) {
         if (wave_on) {
-            // per-channel sums over the 32 pixel lanes of a half: butterfly reduce-scatter; afterwards lane L holds channel index
-            // kk = 8 b4 + 4 b3 + 2 b2 + b1 (bN = bit N of L), lanes L and L ^ 1 the same total
-            auto stage = [&](float (&v)[16], auto W) {
-                constexpr int w = decltype(W)::value;
-                const bool hi = (lane & (2 * w)) != 0;
-#pragma unroll
-                for (int k = 0; k < w; ++k) {
-                    const float send = hi ? v[k] : v[k + w];
-                    const float keep = hi ? v[k + w] : v[k];
-                    v[k] = keep + __shfl_xor(send, 2 * w, 64);
-                }
-            };
-            auto reduce16 = [&](float (&v)[16]) {
-                stage(v, std::integral_constant<int, 8>{});
-                stage(v, std::integral_constant<int, 4>{});
-                stage(v, std::integral_constant<int, 2>{});
-                stage(v, std::integral_constant<int, 1>{});
-                v[0] += __shfl_xor(v[0], 1, 64);
-            };
-            reduce16(s1);
-            reduce16(s2);
+            reduce_scatter16(s1, lane);
+            reduce_scatter16(s2, lane);
         }
         // the pixel tiles of a workgroup that share their output channels (WPX waves) meet in LDS: ONE atomic per statistic, channel and workgroup
         __shared__ float s_st[4][2][32];
         if (wk == 0) {
-            const int kk = ((lane >> 4) & 1) * 8 + ((lane >> 3) & 1) * 4 + ((lane >> 2) & 1) * 2 + ((lane >> 1) & 1);
+            const int kk = reduce_scatter16_index(lane);
             const int ch = 4 * fhalf + 8 * (kk >> 2) + (kk & 3);
             if ((lane & 1) == 0) { s_st[wave][0][ch] = wave_on ? s1[0] : 0.f; s_st[wave][1][ch] = wave_on ? s2[0] : 0.f; }
         }
@@ -213,8 +181,7 @@ __global__ __launch_bounds__(256, MT == 2 ? 1 : 2) void conv_lean_kernel(const m
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wk = wave % KS, wco = (wave / KS) % WCO, wpx = wave / (KS * WCO);
-    const int per_xcd = (int)gridDim.x >> 3;
-    const int lin = (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);      // an XCD's L2 sees a contiguous run of patches
+    const int lin = xcd_tile_index();      // an XCD's L2 sees a contiguous run of patches
     const bool wg_on = lin < total_tiles;                // (a workgroup past the end still walks the code on clamped indices: fused_bn_finalize counts tickets)
     const int lin_c = wg_on ? lin : 0;
     const int tile_n = lin_c % tiles_n;
@@ -265,18 +232,10 @@ __global__ __launch_bounds__(256, MT == 2 ? 1 : 2) void conv_lean_kernel(const m
         v = a_inb[j] ? v : z;
         u32x2 p1, p2, p3;
         if constexpr (NP == 1) {
-            p1[0] = lean_rne16(v.x) | (lean_rne16(v.y) << 16);
-            p1[1] = lean_rne16(v.z) | (lean_rne16(v.w) << 16);
+            p1[0] = rne16(v.x) | (rne16(v.y) << 16);
+            p1[1] = rne16(v.z) | (rne16(v.w) << 16);
         } else {
-            const float xs[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const float a = xs[2 * h], b = xs[2 * h + 1];
-                p1[h] = lean_pack_hi16(a, b);
-                const float ar = lean_chop_rest(a), br = lean_chop_rest(b);
-                p2[h] = lean_pack_hi16(ar, br);
-                p3[h] = lean_pack_hi16(lean_chop_rest(ar), lean_chop_rest(br));
-            }
+            bf16_pieces<NP>(v, p1, p2, p3);
         }
         if (a_val[j]) {
             unsigned char* dst = smem + sc * (KS * CHB) + a_loff[j];
@@ -338,8 +297,6 @@ __global__ __launch_bounds__(256, MT == 2 ? 1 : 2) void conv_lean_kernel(const m
             for (int pc = 0; pc < NPC; ++pc) af[buf][i][pc] = *reinterpret_cast<const bf16x8*>(A + pc * APLANE + i * (G::TR * HP * 16));
     };
     // six products (weights piece PB x activation piece PA), smallest first; t < 3 -> acc[..][1]
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0};
-    constexpr int PB[6] = {0, 2, 1, 0, 1, 0};
     auto mfma_step = [&](int buf, int slot) {
         bf16x8 b[NPC];
 #pragma unroll
@@ -442,8 +399,7 @@ __global__ __launch_bounds__(256, 2) void gemm_lean_kernel(const mrfa_conv_param
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wk = wave % KS, wco = wave / KS;
-    const int per_xcd = (int)gridDim.x >> 3;
-    const int lin = (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);
+    const int lin = xcd_tile_index();
     const bool wg_on = lin < total_tiles;
     const int lin_c = wg_on ? lin : 0;
     const int tile_n = lin_c % tiles_n;
@@ -475,20 +431,7 @@ __global__ __launch_bounds__(256, 2) void gemm_lean_kernel(const mrfa_conv_param
         for (int j = 0; j < NU; ++j) {
             const f32x4 v = a_ok[j] ? ra[j] : z;
             u32x2 p1, p2, p3;
-            if constexpr (NP == 1) {
-                p1[0] = lean_rne16(v.x) | (lean_rne16(v.y) << 16);
-                p1[1] = lean_rne16(v.z) | (lean_rne16(v.w) << 16);
-            } else {
-                const float xs[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const float a = xs[2 * h], b = xs[2 * h + 1];
-                    p1[h] = lean_pack_hi16(a, b);
-                    const float ar = lean_chop_rest(a), br = lean_chop_rest(b);
-                    p2[h] = lean_pack_hi16(ar, br);
-                    p3[h] = lean_pack_hi16(lean_chop_rest(ar), lean_chop_rest(br));
-                }
-            }
+            bf16_pieces<NP>(v, p1, p2, p3);
             unsigned char* dst = smem + buf * STAGE + a_loff[j];
             *reinterpret_cast<u32x2*>(dst) = p1;
             if constexpr (NPC >= 2) *reinterpret_cast<u32x2*>(dst + APLANE) = p2;
@@ -519,8 +462,6 @@ __global__ __launch_bounds__(256, 2) void gemm_lean_kernel(const mrfa_conv_param
         for (int k = 0; k < 2; ++k)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][k][r] = 0.f;
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0};
-    constexpr int PB[6] = {0, 2, 1, 0, 1, 0};
     const int a_frag = wk * (2 * CHB) + fhalf * AHALF + frow * 16;        // + i * 32 * 16 per row tile, + h * CHB per k16 step
     auto compute = [&](int buf, auto SET) {
         constexpr int set = decltype(SET)::value;

@@ -44,11 +44,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void conv_mfma_kernel(const
     const int wave = tid >> 6;
     const int wm = wave / WAVES_N;
     const int wn = wave % WAVES_N;
-    // XCD-aware tile order: workgroup b runs on XCD b % 8 (each XCD has a private 4 MiB L2).  Give every XCD one
-    // contiguous band of output tiles so the 3x3 halo rows and the tile's Cout-siblings are re-read from ITS L2
-    // instead of being fetched by all eight.
-    const int per_xcd = (int)gridDim.x >> 3;
-    const int lin = (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);
+    const int lin = xcd_tile_index();
     if (lin >= total_tiles) return;
     const int tile_m = lin / tiles_n;
     const int tile_n = lin - tile_m * tiles_n;

@@ -16,44 +16,13 @@
 //   padding (48 KB per workgroup, 3 workgroups = 12 waves per CU) -> 12 fragment reads and 24 MFMAs per k16 step per wave.
 // Epilogue identical to conv_mfma.hip (C/D layout of the 32x32 MFMAs does not depend on the input type).
 #include <type_traits>
-#include "common.h"
+#include "mfma_bf16.h"
 
 namespace {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int BM = 128, NT = 256;
 constexpr int PLANE = 128 * 32;                    // bytes per (operand, piece) plane of one k16 slab: 128 rows x 16 bf16
 constexpr int SLAB = 6 * PLANE;                    // A pieces 1..3, B pieces 1..3
-
-__device__ __forceinline__ unsigned pack_hi16(float a, float b) {      // (bf16 chop of b) << 16 | (bf16 chop of a)
-    return __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u);
-}
-__device__ __forceinline__ float chop_rest(float x) { return x - __uint_as_float(__float_as_uint(x) & 0xffff0000u); }
-
-// 4 consecutive k of one row -> the three bf16x4 pieces (2 dwords each)
-__device__ __forceinline__ void split3(const f32x4 v, u32x2& p1, u32x2& p2, u32x2& p3) {
-    const float x[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const float a = x[2 * q], b = x[2 * q + 1];
-        p1[q] = pack_hi16(a, b);
-        const float ra = chop_rest(a), rb = chop_rest(b);
-        p2[q] = pack_hi16(ra, rb);
-        p3[q] = pack_hi16(chop_rest(ra), chop_rest(rb));
-    }
-}
-
-// plain bf16 operands (NP = 1): round-to-nearest-even of the fp32 value, one product -- the arithmetic of a bf16 autocast
-__device__ __forceinline__ unsigned rne16(float x) {
-    const unsigned u = __float_as_uint(x);
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-__device__ __forceinline__ void round1(const f32x4 v, u32x2& p1) {
-    p1[0] = rne16(v.x) | (rne16(v.y) << 16);
-    p1[1] = rne16(v.z) | (rne16(v.w) << 16);
-}
 
 // BN = 128: waves 2 x 2, each 64 x 64.  BN = 64 (layers with 64 output channels: half of a 128-wide tile would be padding):
 // waves 2 x 2, each 64 x 32 -- same loaders, the B operand simply has 64 rows.
@@ -70,8 +39,7 @@ __global__ __launch_bounds__(NT, 3) void conv_bf16x6_kernel(const mrfa_conv_para
     const int lane = tid & 63;
     const int wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    const int per_xcd = (int)gridDim.x >> 3;
-    const int lin = (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);
+    const int lin = xcd_tile_index();
     if (lin >= total_tiles) return;
     const int tile_m = lin / tiles_n;
     const int tile_n = lin - tile_m * tiles_n;
@@ -110,7 +78,6 @@ __global__ __launch_bounds__(NT, 3) void conv_bf16x6_kernel(const mrfa_conv_para
     f32x4 ra[2][2], rb[2][2], psc[2], psh[2];      // [row j][slab h]
     // WS: weights arrive pre-split (pack modes 8 / 9): thread (brow = tid >> 1, bhalf = tid & 1) copies, per slab and piece,
     // the 8 bf16 of row brow that form one MFMA fragment half -- no VALU work on the B operand at all
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     u32x4 wsp[2][3];
     const int brow = tid >> 1, bhalf = tid & 1;
     const bool b_loader = brow < BN;
@@ -197,20 +164,17 @@ __global__ __launch_bounds__(NT, 3) void conv_bf16x6_kernel(const mrfa_conv_para
             }
             v = a_inb[j] ? v : z;
             u32x2 p1, p2, p3;
-            if constexpr (NP == 1) {
-                round1(v, p1);
-                *reinterpret_cast<u32x2*>(base + 0 * PLANE + off) = p1;
-                static_assert(NP != 1 || !WS, "the pre-split weight pieces are truncations: plain bf16 rounds the fp32 weights itself");
-                round1(b_ok[j] ? rb[j][h] : z, p1);
-                *reinterpret_cast<u32x2*>(base + 3 * PLANE + off) = p1;
-            } else {
-                split3(v, p1, p2, p3);
-                *reinterpret_cast<u32x2*>(base + 0 * PLANE + off) = p1;
+            static_assert(NP != 1 || !WS, "the pre-split weight pieces are truncations: plain bf16 rounds the fp32 weights itself");
+            bf16_pieces<NP>(v, p1, p2, p3);
+            *reinterpret_cast<u32x2*>(base + 0 * PLANE + off) = p1;
+            if constexpr (NP != 1) {
                 *reinterpret_cast<u32x2*>(base + 1 * PLANE + off) = p2;
                 *reinterpret_cast<u32x2*>(base + 2 * PLANE + off) = p3;
-                if constexpr (!WS) {
-                    split3(b_ok[j] ? rb[j][h] : z, p1, p2, p3);
-                    *reinterpret_cast<u32x2*>(base + 3 * PLANE + off) = p1;
+            }
+            if constexpr (!WS) {
+                bf16_pieces<NP>(b_ok[j] ? rb[j][h] : z, p1, p2, p3);
+                *reinterpret_cast<u32x2*>(base + 3 * PLANE + off) = p1;
+                if constexpr (NP != 1) {
                     *reinterpret_cast<u32x2*>(base + 4 * PLANE + off) = p2;
                     *reinterpret_cast<u32x2*>(base + 5 * PLANE + off) = p3;
                 }
@@ -254,8 +218,6 @@ __global__ __launch_bounds__(NT, 3) void conv_bf16x6_kernel(const mrfa_conv_para
             for (int pc = 0; pc < NPC; ++pc) b[pc][j] = *reinterpret_cast<const bf16x8*>(base + (3 + pc) * PLANE + off);
         }
         // six products, smallest first; the four accumulators interleave so no MFMA waits for its predecessor
-        constexpr int PA[6] = {2, 0, 1, 1, 0, 0};
-        constexpr int PB[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
         for (int t = 6 - NP; t < 6; ++t)                    // NP = 3: a1*b0 + a0*b1 + a0*b0 (drops the three ~2^-16 terms)
 #pragma unroll
@@ -470,7 +432,7 @@ __global__ __launch_bounds__(NT, 3) void conv_bf16x6_kernel(const mrfa_conv_para
             }
         }
         if (p.stats && !splitk) {
-            // per-channel sums over the 32 pixel lanes of a half: butterfly reduce-scatter (see conv_halo.hip); afterwards lane L holds
+            // per-channel sums over the 32 pixel lanes of a half: butterfly reduce-scatter (as reduce_scatter16 of mfma_bf16.h); afterwards lane L holds
             // channel index kk = 8 b4 + 4 b3 + 2 b2 + b1 (bN = bit N of L)
             auto stage = [&](float (&v)[16], auto W) {
                 constexpr int w = decltype(W)::value;

@@ -1,6 +1,6 @@
 // Layout kernels: conv-weight (un)packing between the reference's OIHW parameters and the MFMA kernel layouts,
 // NCHW <-> NHWC conversion at the module boundary, strided view copies.  All HBM-bound, all tiny next to the convs.
-#include "common.h"
+#include "mfma_bf16.h"
 
 namespace {
 
@@ -145,13 +145,10 @@ __global__ void copy_view_vec_kernel(const float* __restrict__ x, int ldx, int C
     }
 }
 
-// fp32 view -> bf16 view, round to nearest, ties to even (the arithmetic of rne16 in conv_halo.hip; a NaN stays a NaN: the rounding carry would turn a
+// fp32 view -> bf16 view, round to nearest, ties to even (rne16 of mfma_bf16.h; a NaN stays a NaN: the rounding carry would turn a
 // payload that sits in the low 16 bits into an infinity).  Streaming: a lane loads eight values (2 x 16 bytes) and stores them as one 16-byte word.
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ unsigned rne16_nan(float x) {
-    const unsigned u = __float_as_uint(x);
-    const unsigned r = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+    const unsigned u = __float_as_uint(x), r = rne16(x);
     return (u & 0x7fffffffu) > 0x7f800000u ? ((u >> 16) | 0x40u) : r;
 }
 

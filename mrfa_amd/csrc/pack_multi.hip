@@ -13,7 +13,7 @@
 // hipGraph without any host->device copy.  A launch lasts as long as ONE workgroup's tile takes (~42 us for a 32 x 32 x 9 tile with three layouts) whatever
 // the number of tiles: the keypoint encoder's ~500 descriptors were 11 launches back to back at the head of every step (0.51 ms), now 3 (0.29 ms).
 #include <type_traits>
-#include "common.h"
+#include "mfma_bf16.h"
 
 namespace {
 
@@ -156,8 +156,7 @@ __global__ __launch_bounds__(256) void pack_multi_kernel(const PackArgs a) {
                     const bool two = f0 + 1 < nf;
                     const float v1 = two ? lds[co_l * row + ci_l * T + t + lstep] : 0.f;
                     if (rne1) {
-                        const unsigned ua = __float_as_uint(v0), ub = __float_as_uint(v1);
-                        const unsigned ra = (ua + 0x7fffu + ((ua >> 16) & 1u)) >> 16, rb = (ub + 0x7fffu + ((ub >> 16) & 1u)) >> 16;
+                        const unsigned ra = rne16(v0), rb = rne16(v1);
                         if (two) *reinterpret_cast<unsigned*>(d16 + idx) = ra | (rb << 16);
                         else d16[idx] = (unsigned short)ra;
                         inner += rows_per_pass;

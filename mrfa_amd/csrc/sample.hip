@@ -5,7 +5,7 @@
 // Replaces aten::grid_sampler_2d (+backward) at modules/util.py:34, dense_motion.py:83, raft.py:166,168,247,260,271,302,
 // aten::upsample_bilinear2d (+backward) at raft.py:161-162,205-206,228,243,266-267,279-295,308 and CorrBlock.__call__
 // (raft.py:23-48) including its avg_pool2d pyramid (raft.py:20) and the two 64 MiB/sample transposes (raft.py:208,235).
-#include "common.h"
+#include "mfma_bf16.h"
 
 namespace {
 
@@ -121,8 +121,6 @@ __global__ __launch_bounds__(256) void grid_sample_fwd_vec_kernel(const float* _
 // each tap is still one 16-byte load but covers twice the channels; LPP = lanes per (pixel, chunk of 8 * LPP channels), LPP = 1 is the general form (any
 // C % 8 == 0: consecutive lanes take consecutive 8-channel groups).  bf16 -> fp32 is exact (a shift / a mask per pair); taps, selection and the blend are
 // grid_sample_fwd_vec_kernel's, in the same order, so the result is that kernel's on the widened input.
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ void widen8(const u32x4 r, f32x4& a, f32x4& b) {
     a.x = __uint_as_float(r.x << 16); a.y = __uint_as_float(r.x & 0xffff0000u);
     a.z = __uint_as_float(r.y << 16); a.w = __uint_as_float(r.y & 0xffff0000u);

@@ -1,5 +1,5 @@
 // Weight gradient of the 3x3 stride-1 "same" convolutions on the bf16 matrix pipe with exactly split fp32 operands (the
-// arithmetic of wgrad_split.hip), ALL NINE TAPS from one staging of the operands:
+// arithmetic of mfma_bf16.h), ALL NINE TAPS from one staging of the operands:
 //
 //   dW[tap (r,s)][co][ci] += alpha * sum_{n,y,x} dY[n,y,x][co] * X'[n, y+r-1, x+s-1][ci]          X' = prologue(ups(x)), zero outside
 //
@@ -24,54 +24,14 @@
 // Used when the conv is 3x3 / pad 1 / stride 1 with Wout % 32 == 0 and Cin % 32 == 0; everything else stays on wgrad_split.hip.
 #include <stdlib.h>
 #include <type_traits>
-#include "common.h"
+#include "mfma_bf16.h"
 
 namespace {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 bf16x4_t;
 
 constexpr int NT = 512;
 constexpr int XPIX = 34;                       // 32 pixels of the strip + one halo pixel on either side
 constexpr int XBLK = XPIX * 64;                // one 32-channel block of an X' row: [34 pixels][32 bf16]
 constexpr int DYBLK = 32 * 64;                 // one 32-channel block of a dY row
-
-__device__ __forceinline__ unsigned pack_hi16(float a, float b) {
-    return __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u);
-}
-__device__ __forceinline__ float chop_rest(float x) { return x - __uint_as_float(__float_as_uint(x) & 0xffff0000u); }
-__device__ __forceinline__ void split3(const f32x4 v, u32x2& p1, u32x2& p2, u32x2& p3) {
-    const float x[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const float a = x[2 * q], b = x[2 * q + 1];
-        p1[q] = pack_hi16(a, b);
-        const float ra = chop_rest(a), rb = chop_rest(b);
-        p2[q] = pack_hi16(ra, rb);
-        p3[q] = pack_hi16(chop_rest(ra), chop_rest(rb));
-    }
-}
-
-__device__ __forceinline__ unsigned rne16(float x) {          // plain bf16 (NP = 1): round to nearest even
-    const unsigned u = __float_as_uint(x);
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-__device__ __forceinline__ void round1(const f32x4 v, u32x2& p1) {
-    p1[0] = rne16(v.x) | (rne16(v.y) << 16);
-    p1[1] = rne16(v.z) | (rne16(v.w) << 16);
-}
-
-// transposing fragment read: rows (pixels) k0 .. k0+7 of this lane's channel column as one MFMA operand (two b64 reads)
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* p) {
-    typedef __attribute__((address_space(3))) bf16x4_t* lds4;
-    const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4)(p));
-    const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4)(p + 4 * 64));
-    bf16x8 r;
-    __builtin_memcpy(&r, &lo, 8);
-    __builtin_memcpy(reinterpret_cast<char*>(&r) + 8, &hi, 8);
-    return r;
-}
 
 // NBO x NBI x TS = 8 waves: BCO = 32 NBO output channels x BCI = 32 NBI input channels per workgroup; TS = 2: the nine taps of a
 // (co, ci) block are split over two waves (taps 0..4 / 5..8) -- the 64 x 64 block shape for layers with <= 64 output channels (a
@@ -101,8 +61,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wt = wave / (NBO * NBI);               // tap half (TS = 2)
     const int wc = (wave / NBI) % NBO, wb = wave % NBI;
-    const int per_xcd = (int)gridDim.x >> 3;
-    const int lin = (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);      // the tiles of one segment share an XCD's L2
+    const int lin = xcd_tile_index();      // the tiles of one segment share an XCD's L2
     if (lin >= total) return;
     const int tile = lin % ntiles;
     int sg = lin / ntiles;
@@ -184,7 +143,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
             const f32x4 z = {0.f, 0.f, 0.f, 0.f};
             v = (row_ok && x_ok[j]) ? v : z;
             u32x2 p1, p2, p3;
-            if constexpr (NP == 1) round1(v, p1); else split3(v, p1, p2, p3);
+            bf16_pieces<NP>(v, p1, p2, p3);
             if (x_val[j]) {
                 *reinterpret_cast<u32x2*>(dst + x_loff[j]) = p1;
                 if constexpr (NPC >= 2) *reinterpret_cast<u32x2*>(dst + NBI * XBLK + x_loff[j]) = p2;
@@ -208,7 +167,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
             for (int e = 0; e < 4; ++e) v[e] = (row_ok && e < d_nval[j]) ? v[e] : 0.f;
             bsum[j] += v;
             u32x2 p1, p2, p3;
-            if constexpr (NP == 1) round1(v, p1); else split3(v, p1, p2, p3);
+            bf16_pieces<NP>(v, p1, p2, p3);
             *reinterpret_cast<u32x2*>(dst + d_loff[j]) = p1;
             if constexpr (NPC >= 2) *reinterpret_cast<u32x2*>(dst + NBO * DYBLK + d_loff[j]) = p2;
             if constexpr (NPC == 3) *reinterpret_cast<u32x2*>(dst + 2 * NBO * DYBLK + d_loff[j]) = p3;
@@ -234,8 +193,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         const unsigned char* D = smD + (oy & 1) * DYROW + a_off;
         const unsigned char* XR[3] = {smX + ((oy + 0) & 3) * XROW + b_off,       // slot of input row oy - 1  (slot = (iy + 1) & 3)
                                       smX + ((oy + 1) & 3) * XROW + b_off, smX + ((oy + 2) & 3) * XROW + b_off};
-        constexpr int PA[6] = {2, 0, 1, 1, 0, 0};
-        constexpr int PB[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
             bf16x8 a[NPC];
@@ -267,8 +224,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         constexpr int Q0 = decltype(Q0_)::value, Q1 = decltype(Q1_)::value, NQ = Q1 - Q0;
         const unsigned char* D = smD + (oy & 1) * DYROW + a_off;
         const unsigned char* XR[2] = {smX + ((oy + ph_y) & 3) * XROW + b_off + ph_x * 64, smX + ((oy + ph_y + 1) & 3) * XROW + b_off + ph_x * 64};
-        constexpr int PA[6] = {2, 0, 1, 1, 0, 0};
-        constexpr int PB[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
             bf16x8 a[NPC], b[NPC][NQ];

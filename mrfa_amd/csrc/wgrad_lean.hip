@@ -18,13 +18,9 @@
 // The prologue is what lets a residual block skip the BatchNorm-apply launch between its two convolutions (conv_lean.hip takes in_scale as well).
 #include <stdlib.h>
 #include <type_traits>
-#include "common.h"
+#include "mfma_bf16.h"
 
 namespace {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 bf16x4_t;
 
 constexpr int WL_MAXP = 24;                        // problems per launch
 
@@ -41,41 +37,6 @@ struct LeanWMulti {
     int prefix[WL_MAXP + 1];                       // first workgroup of problem i
     LeanW p[WL_MAXP];
 };
-
-__device__ __forceinline__ unsigned wl_pack_hi16(float a, float b) { return __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u); }
-__device__ __forceinline__ float wl_chop_rest(float x) { return x - __uint_as_float(__float_as_uint(x) & 0xffff0000u); }
-__device__ __forceinline__ unsigned wl_rne16(float x) {
-    const unsigned u = __float_as_uint(x);
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-template <int NP>
-__device__ __forceinline__ void wl_pieces(const f32x4 v, u32x2& p1, u32x2& p2, u32x2& p3) {
-    if constexpr (NP == 1) {
-        p1[0] = wl_rne16(v.x) | (wl_rne16(v.y) << 16);
-        p1[1] = wl_rne16(v.z) | (wl_rne16(v.w) << 16);
-    } else {
-        const float xs[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const float a = xs[2 * h], b = xs[2 * h + 1];
-            p1[h] = wl_pack_hi16(a, b);
-            const float ar = wl_chop_rest(a), br = wl_chop_rest(b);
-            p2[h] = wl_pack_hi16(ar, br);
-            p3[h] = wl_pack_hi16(wl_chop_rest(ar), wl_chop_rest(br));
-        }
-    }
-}
-
-// transposing fragment read: pixels k0 .. k0+7 of this lane's channel column as one MFMA operand (two b64 reads; see wgrad_halo.hip)
-__device__ __forceinline__ bf16x8 wl_tr_frag(const unsigned char* p) {
-    typedef __attribute__((address_space(3))) bf16x4_t* lds4;
-    const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4)(p));
-    const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4)(p + 4 * 64));
-    bf16x8 r;
-    __builtin_memcpy(&r, &lo, 8);
-    __builtin_memcpy(reinterpret_cast<char*>(&r) + 8, &hi, 8);
-    return r;
-}
 
 // NB: 32-channel blocks per side of the workgroup's weight block (1: 32 x 32, the four waves take four pixel tiles; 2: 64 x 64, one block pair per wave)
 // TW: patch width (32: a pixel tile is one row of 32; 16: two rows of 16)
@@ -188,7 +149,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_lean_kernel(const LeanWMulti a) 
             }
             v = (okmask >> j) & 1u ? v : z;
             u32x2 p1, p2, p3;
-            wl_pieces<NP>(v, p1, p2, p3);
+            bf16_pieces<NP>(v, p1, p2, p3);
             if (val) {
                 unsigned char* dst = smX + blk * XBLK + hp * 64 + quad * 8;
                 *reinterpret_cast<u32x2*>(dst) = p1;
@@ -201,7 +162,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_lean_kernel(const LeanWMulti a) 
             const bool val = d_unit(j, blk, px, quad);
             const f32x4 v = (okmask >> (16 + j)) & 1u ? rd[j] : z;
             u32x2 p1, p2, p3;
-            wl_pieces<NP>(v, p1, p2, p3);
+            bf16_pieces<NP>(v, p1, p2, p3);
             if (val) {
                 unsigned char* dst = smD + blk * DBLK + px * 64 + quad * 8;
                 *reinterpret_cast<u32x2*>(dst) = p1;
@@ -223,8 +184,6 @@ __global__ __launch_bounds__(256, 1) void wgrad_lean_kernel(const LeanWMulti a) 
     const int frag_off = (8 * (grp16 >> 1) + (l16 >> 2)) * 64 + (grp16 & 1) * 32 + (l16 & 3) * 8;
     const int a_off = wco * DBLK + wpx * (32 * 64) + frag_off;                    // + kk * 16 * 64
     const int b_off = wci * XBLK + frag_off;
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0};
-    constexpr int PB[6] = {0, 2, 1, 0, 1, 0};
     constexpr int TG = 3, NGRP = 3;                // taps per fragment group, groups per k16 step
     constexpr int NUNIT = NX + ND, UPG = (NUNIT + 2 * NGRP - 1) / (2 * NGRP);      // staging units stored behind each of the 2 x 3 tap groups
     // patch in buffer `buf` x this wave's nine tap tiles; `stage`: the next patch (in the registers) goes to the other buffer, a few units per tap group
@@ -237,7 +196,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_lean_kernel(const LeanWMulti a) 
             const int row0 = TW == 32 ? wpx : wpx * 2 + kk, col0 = TW == 32 ? 16 * kk : 0;
             bf16x8 af[NPC];
 #pragma unroll
-            for (int pc = 0; pc < NPC; ++pc) af[pc] = wl_tr_frag(smD + pc * DPLANE + a_off + kk * 16 * 64);
+            for (int pc = 0; pc < NPC; ++pc) af[pc] = tr_frag(smD + pc * DPLANE + a_off + kk * 16 * 64);
 #pragma unroll
             for (int gi = 0; gi < NGRP; ++gi) {
                 const int g0 = gi * TG;
@@ -246,7 +205,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_lean_kernel(const LeanWMulti a) 
                 for (int q = 0; q < TG; ++q) {
                     const int tap = g0 + q, r = tap / 3, s = tap - 3 * r;
 #pragma unroll
-                    for (int pc = 0; pc < NPC; ++pc) bfr[pc][q] = wl_tr_frag(smX + pc * XPLANE + b_off + ((row0 + r) * HP + col0 + s) * 64);
+                    for (int pc = 0; pc < NPC; ++pc) bfr[pc][q] = tr_frag(smX + pc * XPLANE + b_off + ((row0 + r) * HP + col0 + s) * 64);
                 }
 #pragma unroll
                 for (int t = 6 - NP; t < 6; ++t)

@@ -1,4 +1,4 @@
-// Weight-gradient convolution on the bf16 matrix pipe with exactly split fp32 operands (see conv_split.hip for the
+// Weight-gradient convolution on the bf16 matrix pipe with exactly split fp32 operands (mfma_bf16.h; see conv_split.hip for the
 // arithmetic: x = x1 + x2 + x3 in bf16 pieces without error, six bf16 MFMA products, fp32 accumulate).
 //
 //   dW[tap][co][ci] += alpha * sum_p dY[p][co] * X'[pix(p) + tap - pad][ci]
@@ -11,12 +11,9 @@
 // and the 16 rows of a ds_read_b128 fragment group both fall on distinct 16-byte bank slots.
 // Covers the cases that dominate the step: 128/64-wide tiles, chunked (not flat) K, Wout % 8 == 0 and N*Hout*Wout % 32 == 0 (every
 // 8-pixel k-group lies in one image row, no partial k-tiles); everything else stays on wgrad_mfma.hip.
-#include "common.h"
+#include "mfma_bf16.h"
 
 namespace {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int WBK = 32;                       // pixels per k-tile (two k16 slabs)
 constexpr int NT = 256;
@@ -24,30 +21,8 @@ constexpr int ROWB = 48;                      // LDS bytes per channel row (32 d
 constexpr int PLANE = 128 * ROWB;             // one piece of one operand of one slab
 constexpr int SLAB = 6 * PLANE + 32;          // A pieces 1..3, B pieces 1..3 (+ skew: SLAB % 128 == 32)
 
-__device__ __forceinline__ unsigned pack_hi16(float a, float b) {
-    return __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u);
-}
-__device__ __forceinline__ float chop_rest(float x) { return x - __uint_as_float(__float_as_uint(x) & 0xffff0000u); }
-
-// 8 consecutive k -> the three bf16x8 pieces
-__device__ __forceinline__ void split3x8(const float (&x)[8], u32x4& p1, u32x4& p2, u32x4& p3) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float a = x[2 * q], b = x[2 * q + 1];
-        p1[q] = pack_hi16(a, b);
-        const float ra = chop_rest(a), rb = chop_rest(b);
-        p2[q] = pack_hi16(ra, rb);
-        p3[q] = pack_hi16(chop_rest(ra), chop_rest(rb));
-    }
-}
-
 // BM x BN in {128 x 128, 64 x 128, 128 x 64}: waves 2 x 2, each (BM/2) x (BN/2); the 64-wide variants serve the layers with 64
 // output or input channels (half of a 128-wide tile would be padding); loader items beyond the tile width stay idle
-__device__ __forceinline__ unsigned rne16(float x) {          // plain bf16 (NP = 1): round to nearest even
-    const unsigned u = __float_as_uint(x);
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-
 template <int BM, int BN, int NP = 6>
 __global__ __launch_bounds__(NT, 2) void wgrad_bf16x6_kernel(const mrfa_wgrad_params p, const long long M, const long long k_per_split,
                                                              const int tiles_n, const int nsplit, const int inner, const int total_splits,
@@ -204,7 +179,7 @@ __global__ __launch_bounds__(NT, 2) void wgrad_bf16x6_kernel(const mrfa_wgrad_pa
                 for (int h = 0; h < 4; ++h) p1[h] = rne16(v[q][2 * h]) | (rne16(v[q][2 * h + 1]) << 16);
                 *reinterpret_cast<u32x4*>(d + 0 * PLANE) = p1;
             } else {
-                split3x8(v[q], p1, p2, p3);
+                bf16_pieces<NP>(v[q], p1, p2, p3);          // 8 consecutive k -> the three bf16x8 pieces
                 *reinterpret_cast<u32x4*>(d + 0 * PLANE) = p1;
                 *reinterpret_cast<u32x4*>(d + 1 * PLANE) = p2;
                 *reinterpret_cast<u32x4*>(d + 2 * PLANE) = p3;
@@ -235,8 +210,6 @@ __global__ __launch_bounds__(NT, 2) void wgrad_bf16x6_kernel(const mrfa_wgrad_pa
 #pragma unroll
             for (int pc = 0; pc < NPC; ++pc)
                 b[pc][j] = *reinterpret_cast<const bf16x8*>(base + (3 + pc) * PLANE + (wn * (TN * 32) + j * 32 + fi) * ROWB);
-        constexpr int PA[6] = {2, 0, 1, 1, 0, 0};
-        constexpr int PB[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
         for (int t = 6 - NP; t < 6; ++t)
 #pragma unroll
