@@ -15,7 +15,7 @@ import contextlib
 import os
 
 import ctypes as C
-from typing import Callable, List, Optional, Sequence
+from typing import Callable, List, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -173,9 +173,7 @@ class DeferredWgrads:
         if not fns:
             return
         sp = hip.stream_ptr()
-        ws = Ctx._wgrad_ws.get((dev, sp))
-        if ws is None:
-            ws = Ctx._wgrad_ws[(dev, sp)] = torch.empty(16 << 20, dtype=torch.float32, device=dev)
+        ws = Ctx._wgrad_scratch(dev, sp)
         arr = (hip.WgradParams * len(fns))()
         for i, fn in enumerate(fns):
             C.memmove(C.byref(arr, i * C.sizeof(hip.WgradParams)), C.byref(fn.params), C.sizeof(hip.WgradParams))
@@ -328,37 +326,6 @@ class stat_groups:
         return False
 
 
-def prepare_packs(module: torch.nn.Module) -> bool:
-    """Refresh, on the current stream, every packed-weight layout the convolutions of `module` have built so far; False if
-    the module has not run forward AND backward yet (layouts and gather tables are then still created lazily, inside the
-    passes) -- the caller must not fork streams in that case."""
-    cws = [m._mrfa_convw for m in module.modules() if getattr(m, "_mrfa_convw", None) is not None]
-    if not cws or any(cw._fwd is None and cw._fo is None for cw in cws) or all(cw._dg is None and cw._fi is None for cw in cws):
-        return False
-    for cw in cws:
-        if cw._fwd is not None:
-            cw.fwd_pack(getattr(cw, "_fwd_padded", False))
-        if cw._dg is not None:
-            cw.dgrad_pack(getattr(cw, "_dg_padded", False))
-        if getattr(cw, "_fwd_s", None) is not None:
-            cw.split_pack("f", getattr(cw, "_fwd_padded", False))
-        if getattr(cw, "_dg_s", None) is not None:
-            cw.split_pack("d", getattr(cw, "_dg_padded", False))
-        if getattr(cw, "_fwd_r", None) is not None:
-            cw.split_pack("f", getattr(cw, "_fwd_padded", False), rne=True)
-        if getattr(cw, "_dg_r", None) is not None:
-            cw.split_pack("d", getattr(cw, "_dg_padded", False), rne=True)
-        if getattr(cw, "_fwd_ph", None) is not None:
-            cw.phase_pack()
-        if getattr(cw, "_dg_ph", None) is not None:
-            cw.phase_pack(dgrad=True)
-        if cw._fo is not None:
-            cw.fewout_pack()
-        if cw._fi is not None:
-            cw.fewin_dgrad_pack()
-    return True
-
-
 class direct_param_grads:
     def __enter__(self):
         global DIRECT_PARAM_GRADS
@@ -376,6 +343,10 @@ def _direct_ok(*params) -> bool:
 
 def _r4(c: int) -> int:
     return (c + 3) // 4 * 4
+
+
+def _up(c: int, m: int) -> int:
+    return (c + m - 1) // m * m
 
 
 def _conv_params() -> hip.ConvParams:
@@ -509,6 +480,58 @@ class ZeroPool:
 
 
 # ------------------------------------------------------------------------------------------------- parameters
+class Gemm(NamedTuple):
+    """One of a convolution's two GEMM directions as the library runs it: `rows` output channels from `K` input channels per tap.
+    "fwd": y = conv(x, w).  "dgrad": dx = conv(dy, w transposed and flipped), a convolution with pad' = R - 1 - pad."""
+    name: str
+    rows: int
+    K: int
+    pad: int
+    flat: bool                     # K % 32 != 0: the flat-K gather (`ktab`) unless the operand is read zero-padded to 32 channels (`padded`)
+    ktab: Callable[[], torch.Tensor]
+
+
+class Layout(NamedTuple):
+    """One packed weight layout of a convolution (the pack-mode table of include/mrfa_hip.h)."""
+    name: str
+    gemm: Optional[str]            # the direction whose [rows padded to 128][K padded to 32] tap matrices it holds; None: [Cout * T * Cin] as they are
+    modes: tuple                   # the pack mode; (chunked, flat-K) for the fp32 layouts
+    dtype: torch.dtype             # int16 = bf16 planes
+    planes: int
+    taps: int                      # tap matrices per plane; 0 = R * S
+    batched: bool                  # only mrfa_pack_conv_weights_multi writes it
+    zeroed: bool                   # allocated zero-filled: nothing ever writes its padding again (PackPlan's refresh does not)
+
+    def mode(self, cw: "ConvW", padded: bool) -> int:
+        return self.modes[len(self.modes) == 2 and cw.gemms[self.gemm].flat and not padded]
+
+    def count(self, cw: "ConvW", padded: bool) -> int:
+        """elements of the buffer"""
+        if self.gemm is None:
+            return cw.T * cw.Cout * cw.Cin
+        g = cw.gemms[self.gemm]
+        if self.mode(cw, padded) != self.modes[0]:
+            return _up(g.rows, 128) * _up(cw.T * g.K, 32)
+        return self.planes * (self.taps or cw.T) * _up(g.rows, 128) * _up(g.K, 32)
+
+
+# THE place to add a layout: ConvW.layout() allocates, packs and caches from an entry, PackPlan refreshes whatever the caches hold, in this order
+_F32, _BF16 = torch.float32, torch.int16
+LAYOUTS = {lay.name: lay for lay in (
+    Layout("fwd", "fwd", (hip.PACK_FWD, hip.PACK_FWD_FLAT), _F32, 1, 0, False, True),
+    Layout("dgrad", "dgrad", (hip.PACK_DGRAD, hip.PACK_DGRAD_FLAT), _F32, 1, 0, False, True),
+    Layout("fwd_split", "fwd", (hip.PACK_FWD_SPLIT,), _BF16, 3, 0, True, True),            # the bf16x6 / bf16x3 kernels' three pieces
+    Layout("dgrad_split", "dgrad", (hip.PACK_DGRAD_SPLIT,), _BF16, 3, 0, True, True),
+    Layout("fwd_rne", "fwd", (hip.PACK_FWD_RNE,), _BF16, 1, 0, True, True),                # plain bf16 mode: one plane rounded to nearest even
+    Layout("dgrad_rne", "dgrad", (hip.PACK_DGRAD_RNE,), _BF16, 1, 0, True, True),
+    # the 16 phase-tap weights of nearest-x2 + a 3x3 conv (UpBlock2d as four 2x2 convolutions on the low-resolution input, util.py:172-176)
+    Layout("fwd_phase", "fwd", (hip.PACK_FWD_PHASE,), _BF16, 3, 16, True, True),
+    Layout("dgrad_phase", "dgrad", (hip.PACK_DGRAD_PHASE,), _BF16, 3, 16, True, True),
+    Layout("fewout", None, (hip.PACK_FEWOUT,), _F32, 1, 0, False, False),                  # [Cout][tap][Cin]
+    Layout("fewin", None, (hip.PACK_FEWIN,), _F32, 1, 0, False, False),                    # [Cin][tap'][Cout]
+)}
+
+
 class ConvW:
     """Packed-weight cache + packed-gradient accumulator for one nn.Conv2d parameter pair (OIHW weight, bias)."""
 
@@ -531,11 +554,9 @@ class ConvW:
         # convs with <= 4 input channels (= a few-output conv over dY)
         self.fewout = self.Cout <= 4 and self.Cin % 4 == 0 and self.R == self.S
         self.fewin = self.Cin <= 4 and self.Cout % 4 == 0 and self.R == self.S
-        self._fo = self._fi = None
-        self._ver_fo = self._ver_fi = None
-        self._fwd = None
-        self._dg = None
-        self._ver_f = self._ver_d = None
+        self.gemms = {"fwd": Gemm("fwd", self.Cout, self.Cin, self.pad, self.fwd_flat, self.ktab_fwd),
+                      "dgrad": Gemm("dgrad", self.Cin, self.Cout, self.R - 1 - self.pad, self.dgrad_flat, self.ktab_dgrad)}
+        self.packs = {}                  # LAYOUTS name -> (buffer, _key() it was packed from, padded): the layouts built so far
         self._ktab_f = None
         self._ktab_d = None
         self.dw_acc: Optional[torch.Tensor] = None
@@ -564,118 +585,34 @@ class ConvW:
         w = self.conv.weight
         return (w._version, w.data_ptr(), CAPTURE_KEY)
 
-    def fwd_pack(self, padded: bool = False) -> torch.Tensor:
-        """padded: chunked layout with Cin zero-padded to a multiple of 32 even though Cin % 32 != 0 (zpad inputs)"""
-        if padded != getattr(self, "_fwd_padded", False):
-            self._fwd = None
-            self._fwd_padded = padded
-        if self._fwd is None or self._ver_f != self._key():
-            w = self.conv.weight.detach()
-            cop = (self.Cout + 127) // 128 * 128
-            if padded:
-                n, mode = self.T * cop * ((self.Cin + 31) // 32 * 32), 0
-            elif self.fwd_flat:
-                kp = (self.T * self.Cin + 31) // 32 * 32
-                n, mode = cop * kp, 1
-            else:
-                n, mode = self.T * cop * self.Cin, 0
-            if self._fwd is None or self._fwd.numel() != n or self._fwd.device != w.device:
-                self._fwd = torch.zeros(n, dtype=torch.float32, device=w.device)      # zero pads: PackPlan never writes them
-            hip.check(hip.lib().mrfa_pack_conv_weight(hip.stream_ptr(), w.contiguous().data_ptr(), self._fwd.data_ptr(),
-                                                      self.Cout, self.Cin, self.R, self.S, mode), "pack(fwd)")
-            self._ver_f = self._key()
-        return self._fwd
-
-    def dgrad_pack(self, padded: bool = False) -> torch.Tensor:
-        if padded != getattr(self, "_dg_padded", False):
-            self._dg = None
-            self._dg_padded = padded
-        if self._dg is None or self._ver_d != self._key():
-            w = self.conv.weight.detach()
-            cip = (self.Cin + 127) // 128 * 128
-            if padded:
-                n, mode = self.T * cip * ((self.Cout + 31) // 32 * 32), 2
-            elif self.dgrad_flat:
-                kp = (self.T * self.Cout + 31) // 32 * 32
-                n, mode = cip * kp, 3
-            else:
-                n, mode = self.T * cip * self.Cout, 2
-            if self._dg is None or self._dg.numel() != n or self._dg.device != w.device:
-                self._dg = torch.zeros(n, dtype=torch.float32, device=w.device)
-            hip.check(hip.lib().mrfa_pack_conv_weight(hip.stream_ptr(), w.contiguous().data_ptr(), self._dg.data_ptr(),
-                                                      self.Cout, self.Cin, self.R, self.S, mode), "pack(dgrad)")
-            self._ver_d = self._key()
-        return self._dg
-
-    def split_pack(self, which: str, padded: bool, rne: bool = False) -> tuple:
-        """(buffer, elements per piece) of the weights pre-split into three bf16 pieces for the bf16x6 kernels (pack mode 8
-        = forward layout, 9 = data-gradient layout); chunked layouts only"""
-        fwd = which == "f"
-        attr, ver = ("_fwd_s", "_ver_fs") if fwd else ("_dg_s", "_ver_ds")
-        if rne:                              # plain bf16 mode: ONE plane rounded to nearest even (pack modes 14 / 15)
-            attr, ver = ("_fwd_r", "_ver_fr") if fwd else ("_dg_r", "_ver_dr")
-        if fwd:
-            rows, cols = (self.Cout + 127) // 128 * 128, (self.Cin + 31) // 32 * 32
-        else:
-            rows, cols = (self.Cin + 127) // 128 * 128, (self.Cout + 31) // 32 * 32
-        piece = self.T * rows * cols
-        npl = 1 if rne else 3
-        buf = getattr(self, attr, None)
+    def layout(self, name: str, padded: bool = False) -> torch.Tensor:
+        """The LAYOUTS[name] buffer, packed from the current weights (a three-plane layout's piece is a third of it).  padded (the fp32 layouts): chunked
+        with K zero-padded to a multiple of 32 although K % 32 != 0 (zpad inputs); there is ONE buffer per layout, so asking with the other `padded`
+        replaces it -- and PackPlan, which may write only buffers it knows, then asks to be rebuilt."""
+        lay = LAYOUTS[name]
+        assert lay.taps == 0 or (self.R == 3 and self.S == 3 and not self.gemms[lay.gemm].flat)
         w = self.conv.weight.detach()
-        if buf is None or buf.numel() != npl * piece or buf.device != w.device:
-            buf = torch.zeros(npl * piece, dtype=torch.int16, device=w.device)
-            setattr(self, attr, buf)
-            setattr(self, ver, None)
-        if getattr(self, ver, None) != self._key():
-            d = hip.PackDesc()
-            d.src, d.Cout, d.Cin, d.R, d.S, d.ndst = w.contiguous().data_ptr(), self.Cout, self.Cin, self.R, self.S, 1
-            d.dst[0], d.mode[0] = buf.data_ptr(), ((14 if fwd else 15) if rne else (8 if fwd else 9))
-            hip.check(hip.lib().mrfa_pack_conv_weights_multi(hip.stream_ptr(), C.pointer(d), 1), "pack(split)")
-            setattr(self, ver, self._key())
-        return buf, (0 if rne else piece)
+        buf, ver, was = self.packs.get(name, (None, None, padded))
+        n = lay.count(self, padded)
+        if buf is None or was != padded or buf.numel() != n or buf.device != w.device:
+            buf, ver = (torch.zeros if lay.zeroed else torch.empty)(n, dtype=lay.dtype, device=w.device), None
+        if ver != self._key():
+            mode = lay.mode(self, padded)
+            if lay.batched:
+                d = hip.PackDesc()
+                d.src, d.Cout, d.Cin, d.R, d.S, d.ndst = w.contiguous().data_ptr(), self.Cout, self.Cin, self.R, self.S, 1
+                d.dst[0], d.mode[0] = buf.data_ptr(), mode
+                hip.check(hip.lib().mrfa_pack_conv_weights_multi(hip.stream_ptr(), C.pointer(d), 1), f"pack({name})")
+            else:
+                hip.check(hip.lib().mrfa_pack_conv_weight(hip.stream_ptr(), w.contiguous().data_ptr(), buf.data_ptr(), self.Cout, self.Cin,
+                                                          self.R, self.S, mode), f"pack({name})")
+            ver = self._key()
+        self.packs[name] = (buf, ver, padded)
+        return buf
 
-    def phase_pack(self, dgrad: bool = False) -> tuple:
-        """(buffer, elements per piece) of the 16 phase-tap weights of nearest-x2 + this 3x3 conv (pack mode 12: UpBlock2d as four 2x2
-        convolutions on the low-resolution input, util.py:172-176), pre-split into three bf16 pieces; dgrad: transposed (mode 13)"""
-        assert self.R == 3 and self.S == 3
-        attr, ver, mode = ("_dg_ph", "_ver_dph", 13) if dgrad else ("_fwd_ph", "_ver_ph", 12)
-        if dgrad:
-            assert not self.dgrad_flat
-            piece = 16 * ((self.Cin + 127) // 128 * 128) * self.Cout
-        else:
-            assert not self.fwd_flat
-            piece = 16 * ((self.Cout + 127) // 128 * 128) * self.Cin
-        buf = getattr(self, attr, None)
-        w = self.conv.weight.detach()
-        if buf is None or buf.numel() != 3 * piece or buf.device != w.device:
-            buf = torch.zeros(3 * piece, dtype=torch.int16, device=w.device)
-            setattr(self, attr, buf)
-            setattr(self, ver, None)
-        if getattr(self, ver, None) != self._key():
-            d = hip.PackDesc()
-            d.src, d.Cout, d.Cin, d.R, d.S, d.ndst = w.contiguous().data_ptr(), self.Cout, self.Cin, self.R, self.S, 1
-            d.dst[0], d.mode[0] = buf.data_ptr(), mode
-            hip.check(hip.lib().mrfa_pack_conv_weights_multi(hip.stream_ptr(), C.pointer(d), 1), "pack(phase)")
-            setattr(self, ver, self._key())
-        return buf, piece
-
-    def _simple_pack(self, attr, ver_attr, mode):
-        if getattr(self, attr) is None or getattr(self, ver_attr) != self._key():
-            w = self.conv.weight.detach()
-            buf = getattr(self, attr)
-            if buf is None or buf.device != w.device:
-                buf = torch.empty(w.numel(), dtype=torch.float32, device=w.device)
-                setattr(self, attr, buf)
-            hip.check(hip.lib().mrfa_pack_conv_weight(hip.stream_ptr(), w.contiguous().data_ptr(), buf.data_ptr(), self.Cout, self.Cin,
-                                                      self.R, self.S, mode), f"pack(mode {mode})")
-            setattr(self, ver_attr, self._key())
-        return getattr(self, attr)
-
-    def fewout_pack(self) -> torch.Tensor:          # [Cout][tap][Cin]
-        return self._simple_pack("_fo", "_ver_fo", 5)
-
-    def fewin_dgrad_pack(self) -> torch.Tensor:     # [Cin][tap'][Cout]
-        return self._simple_pack("_fi", "_ver_fi", 7)
+    def built(self):
+        """(Layout, buffer, padded) of the layouts built so far, in LAYOUTS order"""
+        return [(lay, self.packs[n][0], self.packs[n][2]) for n, lay in LAYOUTS.items() if n in self.packs]
 
     def grad_acc(self, pool: Optional[ZeroPool] = None):
         if self.dw_acc is None:
@@ -694,7 +631,7 @@ class ConvW:
         accumulator is un-packed INTO weight.grad (+=) and (None, None) is returned."""
         if self.dw_acc is None:
             return None, None
-        mode = 6 if self.fewout else 4
+        mode = hip.UNPACK_ACC_FEWOUT if self.fewout else hip.UNPACK_ACC
         if self._direct:
             hip.check(hip.lib().mrfa_pack_conv_weight(hip.stream_ptr(), self.dw_acc.data_ptr(), self.conv.weight.grad.data_ptr(), self.Cout,
                                                       self.Cin, self.R, self.S, mode), "unpack(wgrad, +=)")
@@ -702,7 +639,7 @@ class ConvW:
             return None, None
         dw = torch.empty_like(self.conv.weight)
         hip.check(hip.lib().mrfa_pack_conv_weight(hip.stream_ptr(), self.dw_acc.data_ptr(), dw.data_ptr(), self.Cout, self.Cin,
-                                                  self.R, self.S, mode | 16), "unpack(wgrad)")
+                                                  self.R, self.S, mode | hip.UNPACK_OVERWRITE), "unpack(wgrad)")
         db = self.db_acc
         self.dw_acc = self.db_acc = None
         return dw, db
@@ -712,7 +649,7 @@ class PackPlan:
     """Every packed layout that exists so far (i.e. after one forward + backward) of every convolution of `model`,
     refreshed from the current weights by ONE batched launch per 48 convolutions (mrfa_pack_conv_weights_multi) instead
     of ~180 single-layout launches; run() also marks the per-convolution caches valid, so the engine's own
-    fwd_pack()/dgrad_pack() calls of the same step find nothing to do."""
+    layout() calls of the same step find nothing to do."""
 
     def __init__(self, model: torch.nn.Module, only: Optional[torch.nn.Module] = None, exclude: Optional[torch.nn.Module] = None):
         """only / exclude: a sub-module of `model` whose convolutions are the plan / are left out of it (GraphedTrainStep packs the keypoint
@@ -725,27 +662,7 @@ class PackPlan:
         for cw in self.cws:
             w = cw.conv.weight
             assert w.is_contiguous()
-            dsts = []
-            if cw._fwd is not None:
-                dsts.append((cw._fwd, 0 if (getattr(cw, "_fwd_padded", False) or not cw.fwd_flat) else 1))
-            if cw._dg is not None:
-                dsts.append((cw._dg, 2 if (getattr(cw, "_dg_padded", False) or not cw.dgrad_flat) else 3))
-            if getattr(cw, "_fwd_s", None) is not None:
-                dsts.append((cw._fwd_s, 8))
-            if getattr(cw, "_dg_s", None) is not None:
-                dsts.append((cw._dg_s, 9))
-            if getattr(cw, "_fwd_r", None) is not None:
-                dsts.append((cw._fwd_r, 14))
-            if getattr(cw, "_dg_r", None) is not None:
-                dsts.append((cw._dg_r, 15))
-            if getattr(cw, "_fwd_ph", None) is not None:
-                dsts.append((cw._fwd_ph, 12))
-            if getattr(cw, "_dg_ph", None) is not None:
-                dsts.append((cw._dg_ph, 13))
-            if cw._fo is not None:
-                dsts.append((cw._fo, 5))
-            if cw._fi is not None:
-                dsts.append((cw._fi, 7))
+            dsts = [(buf, lay.mode(cw, padded)) for lay, buf, padded in cw.built()]
             for i in range(0, len(dsts), 3):
                 d = hip.PackDesc()
                 d.src, d.Cout, d.Cin, d.R, d.S = w.data_ptr(), cw.Cout, cw.Cin, cw.R, cw.S
@@ -759,13 +676,11 @@ class PackPlan:
         self.table = (hip.PackDesc * max(self.n, 1))(*descs)
         self.ptrs = [(cw, cw.conv.weight.data_ptr()) + self._buffer_ids(cw) for cw in self.cws]
 
-    _PLANES = ("_fwd", "_dg", "_fwd_s", "_dg_s", "_fwd_r", "_dg_r", "_fwd_ph", "_dg_ph", "_fo", "_fi")
-
-    @classmethod
-    def _buffer_ids(cls, cw) -> tuple:
+    @staticmethod
+    def _buffer_ids(cw) -> tuple:
         """identity of every packed layout the plan may write: a layout created (or re-allocated) after the plan was built is not in
         the plan's table, and stamping its version below would make the engine skip the pack it needs -- stale weights under replay"""
-        return tuple(id(getattr(cw, a, None)) for a in cls._PLANES)
+        return tuple(id(buf) for _, buf, _ in cw.built())
 
     def run(self):
         if self.n:
@@ -774,7 +689,7 @@ class PackPlan:
             cw, wptr, ids = rec[0], rec[1], rec[2:]
             assert cw.conv.weight.data_ptr() == wptr and self._buffer_ids(cw) == ids, "PackPlan is stale: rebuild it"
             k = cw._key()
-            cw._ver_f = cw._ver_d = cw._ver_fo = cw._ver_fi = cw._ver_fs = cw._ver_ds = cw._ver_ph = cw._ver_dph = cw._ver_fr = cw._ver_dr = k
+            cw.packs = {name: (buf, k, padded) for name, (buf, _, padded) in cw.packs.items()}
 
 
 def unpack_direct(cws: List["ConvW"], accs: Optional[List[torch.Tensor]] = None):
@@ -997,19 +912,37 @@ class Ctx:
         if self.record:
             self.tape.append(fn)
 
-    def _launch_conv(self, p, what: str, alg_cin: Optional[int] = None):
+    @staticmethod
+    def _timed(launch, entry):
+        """launch(); while bench.py collects a profile (Ctx.profile), between two timing events and recorded as entry() = (config, flops, text)"""
         prof = Ctx.profile
         if prof is None:
-            self._chk(self.L.mrfa_conv2d_nhwc(self.s, C.byref(p)), what)
+            launch()
             return
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        self._chk(self.L.mrfa_conv2d_nhwc(self.s, C.byref(p)), what)
+        launch()
         e1.record()
+        config, flops, what = entry()
+        prof.append((config, flops, e0, e1, what))
+
+    def _launch_conv(self, p, what: str, alg_cin: Optional[int] = None):
         nb = max(p.nbatch, 1)
-        flops = 2.0 * nb * p.N * p.Hout * p.Wout * p.Cout * (alg_cin or p.Cin) * p.R * p.S      # algorithmic (unpadded)
-        prof.append((self.L.mrfa_conv2d_last_config(), flops, e0, e1,
-                     f"{what} {p.Cin}->{p.Cout} {p.R}x{p.S} @{p.Hout}x{p.Wout} N={p.N} nb={nb} ups={p.ups}"))
+        self._timed(lambda: self._chk(self.L.mrfa_conv2d_nhwc(self.s, C.byref(p)), what),
+                    lambda: (self.L.mrfa_conv2d_last_config(), 2.0 * nb * p.N * p.Hout * p.Wout * p.Cout * (alg_cin or p.Cin) * p.R * p.S,      # algorithmic (unpadded)
+                             f"{what} {p.Cin}->{p.Cout} {p.R}x{p.S} @{p.Hout}x{p.Wout} N={p.N} nb={nb} ups={p.ups}"))
+
+    @staticmethod
+    def _wgrad_scratch(dev, stream) -> torch.Tensor:
+        """the 64 MiB scratch of the two-stage weight-gradient split reduction, one per stream: concurrent passes must not share it"""
+        ws = Ctx._wgrad_ws.get((dev, stream))
+        if ws is None:
+            ws = Ctx._wgrad_ws[(dev, stream)] = torch.empty(16 << 20, dtype=torch.float32, device=dev)
+        return ws
+
+    def _touch(self, cw: ConvW):
+        if cw not in self.touched_convs:
+            self.touched_convs.append(cw)
 
     def new(self, N, H, W, C_, ld=None, zero=False, pad32=False) -> View:
         if pad32 and C_ % 32 != 0:
@@ -1102,7 +1035,7 @@ class Ctx:
                   and x.ld % 4 == 0 and x.coff % 4 == 0)
         if direct:
             out = out or self.new(x.N, Ho, Wo, cw.Cout)
-            self._chk(self.L.mrfa_conv_fewout_fwd(self.s, x.ptr, x.ld, x.N, x.H, x.W, cw.Cin, cw.fewout_pack().data_ptr(),
+            self._chk(self.L.mrfa_conv_fewout_fwd(self.s, x.ptr, x.ld, x.N, x.H, x.W, cw.Cin, cw.layout("fewout").data_ptr(),
                                                   bias.data_ptr() if bias is not None else None, out.ptr, out.ld, cw.Cout, cw.R, cw.pad, 0),
                       "conv_fewout_fwd")
             if self.record:
@@ -1123,36 +1056,16 @@ class Ctx:
                     if need_dx:
                         self._conv_dgrad(x, cw, out, ups, pre, relu_in)
                 self.tape.append(bwd_direct)
-                if cw not in self.touched_convs:
-                    self.touched_convs.append(cw)
+                self._touch(cw)
             return out
         p = _conv_params()
         p.x, p.ldx, p.Hin, p.Win, p.ups, p.N, p.Cin = x.ptr, x.ld, x.H, x.W, int(ups), x.N, cw.Cin
         padded = cw.fwd_flat and x.zpad and x.coff % 4 == 0 and pre is None
-        cop = (cw.Cout + 127) // 128 * 128
-        if padded:
-            cip32 = (cw.Cin + 31) // 32 * 32
-            p.Cin = cip32
-            p.w_ld, p.w_tap, p.kflat = cip32, cop * cip32, 0
-            if self.split or self.bf16:
-                ws, p.w_piece = cw.split_pack("f", True, rne=self.bf16)
-                p.w_split = ws.data_ptr()
-        elif cw.fwd_flat:
-            kp = (cw.T * cw.Cin + 31) // 32 * 32
-            p.w_ld, p.w_tap, p.kflat = kp, 0, cw.T * cw.Cin
-            p.ktab = cw.ktab_fwd().data_ptr()
-        else:
-            p.w_ld, p.w_tap, p.kflat = cw.Cin, cop * cw.Cin, 0
-            if self.split or self.bf16:
-                ws, p.w_piece = cw.split_pack("f", False, rne=self.bf16)
-                p.w_split = ws.data_ptr()
-                if self.split and ups and cw.R == 3 and cw.S == 3 and cw.pad == 1 and PHASE_UPCONV:
-                    # UpBlock2d: the library may run nearest-x2 + 3x3 as four 2x2 phase convolutions (16 / 36 of the MACs, csrc/conv_halo.hip)
-                    wph, p.w_phase_piece = cw.phase_pack()
-                    p.w_phase = wph.data_ptr()
-        p.w_rows = cop
-        # the fp32 weight layout only where the kernel this call runs reads it (_fp32_weights below): a placeholder until the block is complete
-        p.w = p.w_split if p.w_split else cw.fwd_pack(padded).data_ptr()
+        fp32 = self._weight_fields(p, cw, "fwd", padded)
+        if self.split and not cw.fwd_flat and ups and cw.R == 3 and cw.S == 3 and cw.pad == 1 and PHASE_UPCONV:
+            # UpBlock2d: the library may run nearest-x2 + 3x3 as four 2x2 phase convolutions (16 / 36 of the MACs, csrc/conv_halo.hip)
+            wph = cw.layout("fwd_phase")
+            p.w_phase, p.w_phase_piece = wph.data_ptr(), wph.numel() // 3
         p.Cout, p.Hout, p.Wout = cw.Cout, Ho, Wo
         p.R, p.S, p.pad = cw.R, cw.S, cw.pad
         if pre is not None:
@@ -1164,17 +1077,11 @@ class Ctx:
         if res is not None:
             p.res, p.ldr = res.ptr, res.ld
         p.alpha, p.nbatch = 1.0, 1
-        late_stats = False
         if stats is not None:
-            p.stats, p.groups = stats.data_ptr(), self.groups
+            p.stats, p.groups = stats.data_ptr(), self.groups        # (before _conv_out: its split-K query is asked about the whole block)
         out = self._conv_out(p, out, x.N, Ho, Wo, cw.Cout)
-        if stats is not None:
-            if self.groups > 1 and not self.L.mrfa_conv2d_groups_supported(C.byref(p)):
-                assert pre is None, "a prologue with statistic groups where the library has none: ask prologue_ok() first"
-                p.stats, p.groups, late_stats = None, 0, True       # (a tile would straddle two groups: one statistics pass per group behind the launch)
-            elif fin is not None:
-                self._fin_params(p, fin, stats, out.rows)
-        self._fp32_weights(p, lambda: cw.fwd_pack(padded))
+        late_stats = self._stats_or_late(p, stats, fin, out.rows, pre)
+        self._fp32_weights(p, fp32)
         self._launch_conv(p, "conv2d", cw.Cin)
         if late_stats:
             self._bn_stats_into(out, stats)
@@ -1193,9 +1100,55 @@ class Ctx:
                 if need_dx:
                     self._conv_dgrad(x, cw, out, ups, pre, relu_in)
             self.tape.append(bwd)
-            if cw not in self.touched_convs:
-                self.touched_convs.append(cw)
+            self._touch(cw)
         return out
+
+    def _weight_fields(self, p, cw: ConvW, gemm: str, padded: bool = False, planes: bool = True, query: Optional[int] = None):
+        """The weight half of a conv parameter block for one GEMM direction of `cw` (cw.gemms): w_ld / w_tap / kflat / ktab / w_rows, the channel count the
+        operand is read with (p.Cin: zero-padded to 32 when `padded`), in the split / bf16 matrix modes the pre-split planes (planes=False: a launch that
+        takes none), and p.w = a PLACEHOLDER where there are planes (see _fp32_weights).  -> the thunk that builds the fp32 layout.
+        query: a pointer of the right alignment to stand in for every weight pointer -- the block is for a capability query and no layout is built."""
+        g = cw.gemms[gemm]
+        rows, k32 = _up(g.rows, 128), _up(g.K, 32)
+        if g.flat and not padded:
+            p.w_ld, p.w_tap, p.kflat = _up(cw.T * g.K, 32), 0, cw.T * g.K
+            p.ktab = g.ktab().data_ptr()
+        else:
+            p.Cin = k32
+            p.w_ld, p.w_tap, p.kflat = k32, rows * k32, 0
+            if planes and (self.split or self.bf16):
+                p.w_piece = 0 if self.bf16 else cw.T * rows * k32
+                p.w_split = query or cw.layout(gemm + ("_rne" if self.bf16 else "_split")).data_ptr()
+        p.w_rows = rows
+        fp32 = lambda: cw.layout(gemm, padded)
+        p.w = query or p.w_split or fp32().data_ptr()
+        return fp32
+
+    def _stats_or_late(self, p, stats, fin, rows: int, pre=None) -> bool:
+        """a forward block whose p.stats / p.groups are set and whose output is known: may the launch accumulate the BatchNorm statistics?  With statistic
+        groups where the library cannot (a tile would straddle two groups) they are taken out of the block -> True: one statistics pass per group behind
+        the launch (_bn_stats_into); else the BatchNorm `fin` is finished inside the launch (_fin_params)."""
+        if stats is None:
+            return False
+        if self.groups > 1 and not self.L.mrfa_conv2d_groups_supported(C.byref(p)):
+            assert pre is None, "a prologue with statistic groups where the library has none: ask prologue_ok() first"
+            p.stats, p.groups = None, 0
+            return True
+        if fin is not None:
+            self._fin_params(p, fin, stats, rows)
+        return False
+
+    @staticmethod
+    def _wgrad_params(x: View, cw: ConvW, dy: int, ldy: int, Ho: int, Wo: int, dw: int, ups=False, stride: int = 0, pre=None) -> hip.WgradParams:
+        """the parameter block of cw's weight gradient from x and dY; pre: (in_scale, in_shift, groups) of a prologue, as pointers"""
+        q = hip.WgradParams()
+        q.x, q.ldx, q.Hin, q.Win, q.ups, q.N, q.Cin = x.ptr, x.ld, x.H, x.W, int(ups), x.N, cw.Cin
+        if pre is not None:
+            q.in_scale, q.in_shift, q.in_relu, q.groups = pre[0], pre[1], 1, pre[2]
+        q.dy, q.ldy, q.Cout, q.Hout, q.Wout = dy, ldy, cw.Cout, Ho, Wo
+        q.R, q.S, q.pad, q.stride = cw.R, cw.S, cw.pad, stride
+        q.dw, q.alpha, q.nbatch, q.ksplit = dw, 1.0, 1, 0
+        return q
 
     def _fp32_weights(self, p, pack):
         """p.w of a complete parameter block whose `w` is still the placeholder (= w_split): the fp32 layout `pack()` only if the kernel this call runs reads
@@ -1237,21 +1190,12 @@ class Ctx:
 
     def _conv_wgrad(self, x: View, cw: ConvW, out: View, ups, pre, has_bias):
         dw, db = cw.grad_acc(self.pool32)
-        q = hip.WgradParams()
-        q.x, q.ldx, q.Hin, q.Win, q.ups, q.N, q.Cin = x.ptr, x.ld, x.H, x.W, int(ups), x.N, cw.Cin
-        if pre is not None:
-            q.in_scale, q.in_shift, q.in_relu = pre[0].data_ptr(), pre[1].data_ptr(), 1
-            q.groups = pre[2].get("groups", 1)
-        q.dy, q.ldy, q.Cout, q.Hout, q.Wout = out.gptr, out.ld, cw.Cout, out.H, out.W
-        q.R, q.S, q.pad = cw.R, cw.S, cw.pad
-        q.dw = dw.data_ptr()
+        q = self._wgrad_params(x, cw, out.gptr, out.ld, out.H, out.W, dw.data_ptr(), ups,
+                               pre=pre and (pre[0].data_ptr(), pre[1].data_ptr(), pre[2].get("groups", 1)))
         q.dbias = db.data_ptr() if (has_bias and db is not None) else None
-        q.alpha, q.nbatch, q.ksplit = 1.0, 1, 0
         if cw.wgrad_flat:
             q.ktab, q.kflat = cw.ktab_fwd().data_ptr(), cw.T * cw.Cin
-        ws = Ctx._wgrad_ws.get((self.dev, self.s))      # per stream: concurrent passes must not share the scratch
-        if ws is None:
-            ws = Ctx._wgrad_ws[(self.dev, self.s)] = torch.empty(16 << 20, dtype=torch.float32, device=self.dev)      # 64 MiB scratch
+        ws = self._wgrad_scratch(self.dev, self.s)
         q.ws, q.ws_bytes = ws.data_ptr(), ws.numel() * 4
         prof = Ctx.profile
         if prof is None and self._defer_ok(cw):
@@ -1259,9 +1203,7 @@ class Ctx:
 
             def launch():
                 st = hip.stream_ptr()
-                w2 = Ctx._wgrad_ws.get((self.dev, st))
-                if w2 is None:
-                    w2 = Ctx._wgrad_ws[(self.dev, st)] = torch.empty(16 << 20, dtype=torch.float32, device=self.dev)
+                w2 = self._wgrad_scratch(self.dev, st)
                 q.ws, q.ws_bytes = w2.data_ptr(), w2.numel() * 4
                 assert keep[0].st.data is not None
                 self._chk(self.L.mrfa_conv2d_wgrad_nhwc(st, C.byref(q)), "wgrad(deferred)")
@@ -1280,12 +1222,8 @@ class Ctx:
         elif prof is None:
             self._chk(self.L.mrfa_conv2d_wgrad_nhwc(self.s, C.byref(q)), "wgrad")
         else:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            self._chk(self.L.mrfa_conv2d_wgrad_nhwc(self.s, C.byref(q)), "wgrad")
-            e1.record()
-            flops = 2.0 * q.N * q.Hout * q.Wout * q.Cout * q.Cin * q.R * q.S
-            prof.append((-1, flops, e0, e1, f"wgrad {q.Cin}->{q.Cout} {q.R}x{q.S} @{q.Hout}x{q.Wout} N={q.N} ups={q.ups} flat={int(q.kflat > 0)} ldx={q.ldx} ldy={q.ldy} xal={x.ptr % 16} dyal={out.gptr % 16} bias={int(bool(q.dbias))} pre={int(pre is not None)}"))
+            self._timed(lambda: self._chk(self.L.mrfa_conv2d_wgrad_nhwc(self.s, C.byref(q)), "wgrad"),
+                        lambda: (-1, 2.0 * q.N * q.Hout * q.Wout * q.Cout * q.Cin * q.R * q.S, f"wgrad {q.Cin}->{q.Cout} {q.R}x{q.S} @{q.Hout}x{q.Wout} N={q.N} ups={q.ups} flat={int(q.kflat > 0)} ldx={q.ldx} ldy={q.ldy} xal={x.ptr % 16} dyal={out.gptr % 16} bias={int(bool(q.dbias))} pre={int(pre is not None)}"))
 
     def _relu_mask_pass(self, x: View):
         """x.grad *= (x > 0): the ReLU backward of x's producers as a pass of its own (where no kernel fuses it)"""
@@ -1301,7 +1239,7 @@ class Ctx:
         first = direct and self._claim(x)             # first writer of x.grad covering all of it: overwrite, no zero fill needed
         if direct and cw.fewin and out.ld % 4 == 0 and out.coff % 4 == 0:
             # few input channels: the data gradient is a few-output conv over dY
-            self._chk(self.L.mrfa_conv_fewout_fwd(self.s, out.gptr, out.ld, out.N, out.H, out.W, cw.Cout, cw.fewin_dgrad_pack().data_ptr(),
+            self._chk(self.L.mrfa_conv_fewout_fwd(self.s, out.gptr, out.ld, out.N, out.H, out.W, cw.Cout, cw.layout("fewin").data_ptr(),
                                                   None, x.gptr, x.ld, cw.Cin, cw.R, cw.R - 1 - cw.pad, 0 if first else 1), "conv_fewout(dgrad)")
             if relu_in:
                 self._relu_mask_pass(x)
@@ -1309,7 +1247,7 @@ class Ctx:
         if (direct and cw.fewout and x.coff % 4 == 0 and
                 self.L.mrfa_conv_fewout_dgrad_supported(cw.Cin, cw.Cout, cw.R, cw.pad, x.W, x.ld)):
             # 3x3 layer with one or two output channels: channel-lane kernel (csrc/conv_fewout3.hip) instead of a K = 9 Cout MFMA GEMM
-            self._chk(self.L.mrfa_conv_fewout_dgrad(self.s, out.gptr, out.ld, out.N, out.H, out.W, cw.Cout, cw.fewout_pack().data_ptr(),
+            self._chk(self.L.mrfa_conv_fewout_dgrad(self.s, out.gptr, out.ld, out.N, out.H, out.W, cw.Cout, cw.layout("fewout").data_ptr(),
                                                     x.gptr, x.ld, cw.Cin, cw.R, cw.pad, 0 if first else 1,
                                                     x.ptr if relu_in else None, x.ld), "conv_fewout_dgrad")
             return
@@ -1319,9 +1257,9 @@ class Ctx:
             # straight into x.grad -- instead of the 3x3 data gradient on the 2H x 2W grid + the 2x2 sum-pooling pass
             q = _conv_params()
             q.x, q.ldx, q.Hin, q.Win, q.ups, q.N, q.Cin = out.gptr, out.ld, out.H, out.W, 2, out.N, cw.Cout
-            cipd = (cw.Cin + 127) // 128 * 128
-            wph, q.w_phase_piece = cw.phase_pack(dgrad=True)
-            q.w_phase = wph.data_ptr()
+            cipd = _up(cw.Cin, 128)
+            wph = cw.layout("dgrad_phase")
+            q.w_phase, q.w_phase_piece = wph.data_ptr(), wph.numel() // 3
             q.w = q.w_phase                                    # (placeholder: the phase kernel reads w_phase only; the ABI's specification reads w: _fp32_weights)
             q.w_ld, q.w_tap, q.kflat, q.w_rows = cw.Cout, cipd * cw.Cout, 0, cipd
             q.Cout, q.Hout, q.Wout = cw.Cin, x.H, x.W
@@ -1331,34 +1269,17 @@ class Ctx:
                 first_ph = self._claim(x)
                 q.y, q.ldy = x.gptr, x.ld
                 q.accumulate = 0 if first_ph else 1
-                self._fp32_weights(q, lambda: cw.dgrad_pack(False))
+                self._fp32_weights(q, lambda: cw.layout("dgrad"))
                 self._launch_conv(q, "dgrad(phase)", cw.Cout)
                 return
         tgt = x if direct else self.new(x.N, Hv, Wv, cw.Cin)
         p = _conv_params()
         p.x, p.ldx, p.Hin, p.Win, p.ups, p.N, p.Cin = out.gptr, out.ld, out.H, out.W, 0, out.N, cw.Cout
-        co32 = (cw.Cout + 31) // 32 * 32
+        co32 = _up(cw.Cout, 32)
         # Cout % 32 != 0 but the dY view sits in a wider (zero-initialised, finite) gradient buffer: read it as co32
         # channels against zero-padded weights instead of taking the scalar-gather flat path
         padded = cw.dgrad_flat and out.coff % 4 == 0 and out.ld % 4 == 0 and out.coff + co32 <= out.ld
-        cip = (cw.Cin + 127) // 128 * 128
-        if padded:
-            p.Cin = co32
-            p.w_ld, p.w_tap, p.kflat = co32, cip * co32, 0
-            if self.split or self.bf16:
-                ws, p.w_piece = cw.split_pack("d", True, rne=self.bf16)
-                p.w_split = ws.data_ptr()
-        elif cw.dgrad_flat:
-            kp = (cw.T * cw.Cout + 31) // 32 * 32
-            p.w_ld, p.w_tap, p.kflat = kp, 0, cw.T * cw.Cout
-            p.ktab = cw.ktab_dgrad().data_ptr()
-        else:
-            p.w_ld, p.w_tap, p.kflat = cw.Cout, cip * cw.Cout, 0
-            if self.split or self.bf16:
-                ws, p.w_piece = cw.split_pack("d", False, rne=self.bf16)
-                p.w_split = ws.data_ptr()
-        p.w_rows = cip
-        p.w = p.w_split if p.w_split else cw.dgrad_pack(padded).data_ptr()       # (placeholder: _fp32_weights below)
+        fp32 = self._weight_fields(p, cw, "dgrad", padded)
         p.y, p.ldy = (tgt.gptr if direct else tgt.ptr), tgt.ld
         p.Cout, p.Hout, p.Wout = cw.Cin, Hv, Wv
         p.R, p.S, p.pad = cw.R, cw.S, cw.R - 1 - cw.pad
@@ -1388,7 +1309,7 @@ class Ctx:
             else:
                 p.stats = p.bst_x = p.bst_scale = p.bst_shift = p.bst_mean = p.bst_invstd = None
                 p.groups = 0
-        self._fp32_weights(p, lambda: cw.dgrad_pack(padded))
+        self._fp32_weights(p, fp32)
         self._launch_conv(p, "dgrad", cw.Cout)
         if relu_in and not fused:
             self._relu_mask_pass(x)
@@ -1683,18 +1604,13 @@ class Ctx:
             return False
         if self.groups <= 1:
             return True
-        cop = (cw.Cout + 127) // 128 * 128
         p = hip.ConvParams()
         p.x, p.ldx, p.Hin, p.Win, p.N, p.Cin = x.ptr, x.ld, x.H, x.W, x.N, cw.Cin
-        p.w = p.w_split = p.in_scale = p.in_shift = p.y = x.ptr           # (placeholders of the right alignment for the query)
-        p.w_ld, p.w_tap, p.w_rows, p.w_piece = cw.Cin, cop * cw.Cin, cop, (0 if self.bf16 else cw.T * cop * cw.Cin)
+        p.in_scale = p.in_shift = p.y = x.ptr                             # (placeholders of the right alignment for the query; the weights likewise)
+        self._weight_fields(p, cw, "fwd", query=x.ptr)
         p.in_relu, p.ldy, p.Cout, p.Hout, p.Wout = 1, _r4(cw.Cout), cw.Cout, x.H + 2 * cw.pad - cw.R + 1, x.W + 2 * cw.pad - cw.S + 1
         p.R, p.S, p.pad, p.alpha, p.nbatch, p.groups = cw.R, cw.S, cw.pad, 1.0, 1, self.groups
-        q = hip.WgradParams()
-        q.x, q.ldx, q.Hin, q.Win, q.N, q.Cin = x.ptr, x.ld, x.H, x.W, x.N, cw.Cin
-        q.in_scale = q.in_shift = q.dy = q.dw = x.ptr
-        q.in_relu, q.ldy, q.Cout, q.Hout, q.Wout, q.R, q.S, q.pad = 1, _r4(cw.Cout), cw.Cout, p.Hout, p.Wout, cw.R, cw.S, cw.pad
-        q.alpha, q.nbatch, q.groups = 1.0, 1, self.groups
+        q = self._wgrad_params(x, cw, x.ptr, _r4(cw.Cout), p.Hout, p.Wout, x.ptr, pre=(x.ptr, x.ptr, self.groups))
         return bool(self.L.mrfa_conv2d_groups_supported(C.byref(p)) and self.L.mrfa_conv2d_wgrad_groups_supported(C.byref(q)))
 
     # -- samplers ---------------------------------------------------------------------------------------------
@@ -2074,31 +1990,22 @@ class Ctx:
         instead of the stride-1 convolution + sub-sampling + statistics passes: a quarter of the MACs forward and in the weight gradient.  The
         data gradient stays the stride-1 one over the zero-stuffed dY.  None: the library has no strided kernel for this shape."""
         Ho, Wo = (x.H + 2 * cw.pad - cw.R) // 2 + 1, (x.W + 2 * cw.pad - cw.S) // 2 + 1
-        cop = (cw.Cout + 127) // 128 * 128
         p = _conv_params()
         p.x, p.ldx, p.Hin, p.Win, p.ups, p.N, p.Cin = x.ptr, x.ld, x.H, x.W, 0, x.N, cw.Cin
-        if cw.fwd_flat:                                # few input channels (the 3 -> 64 stem, hr_base.py:302): the fp32 tile kernel's flat-K gather, strided
-            p.w_ld, p.w_tap, p.kflat, p.w_rows = (cw.T * cw.Cin + 31) // 32 * 32, 0, cw.T * cw.Cin, cop
-            p.ktab = cw.ktab_fwd().data_ptr()
-        else:
-            p.w_ld, p.w_tap, p.kflat, p.w_rows = cw.Cin, cop * cw.Cin, 0, cop
+        # the fp32 kernels only (flat-K, strided, for few input channels: the 3 -> 64 stem, hr_base.py:302); placeholders of the right alignment for the query
+        fp32 = self._weight_fields(p, cw, "fwd", planes=False, query=x.ptr)
         p.Cout, p.Hout, p.Wout = cw.Cout, Ho, Wo
         p.R, p.S, p.pad, p.stride = cw.R, cw.S, cw.pad, 2
         p.alpha, p.nbatch, p.splitk = 1.0, 1, 1
-        p.y, p.ldy = x.ptr, _r4(cw.Cout)              # (placeholders of the right alignment for the query)
-        p.w = x.ptr
+        p.y, p.ldy = x.ptr, _r4(cw.Cout)
         if not self.L.mrfa_conv2d_stride_supported(C.byref(p)):
             return None
         out = self.new(x.N, Ho, Wo, cw.Cout)
-        p.w = cw.fwd_pack(False).data_ptr()
+        p.w = fp32().data_ptr()
         p.y, p.ldy = out.ptr, out.ld
-        late_stats = False
         if stats is not None:
             p.stats, p.groups = stats.data_ptr(), self.groups
-            if self.groups > 1 and not self.L.mrfa_conv2d_groups_supported(C.byref(p)):
-                p.stats, p.groups, late_stats = None, 0, True
-            elif fin is not None:
-                self._fin_params(p, fin, stats, out.rows)
+        late_stats = self._stats_or_late(p, stats, fin, out.rows)
         self._launch_conv(p, "conv2d(stride 2)", cw.Cin)
         if late_stats:
             self._bn_stats_into(out, stats)
@@ -2108,11 +2015,7 @@ class Ctx:
                     return
                 if conv.weight.requires_grad:
                     dw, db = cw.grad_acc(self.pool32)
-                    q = hip.WgradParams()
-                    q.x, q.ldx, q.Hin, q.Win, q.ups, q.N, q.Cin = x.ptr, x.ld, x.H, x.W, 0, x.N, cw.Cin
-                    q.dy, q.ldy, q.Cout, q.Hout, q.Wout = out.gptr, out.ld, cw.Cout, Ho, Wo
-                    q.R, q.S, q.pad, q.stride = cw.R, cw.S, cw.pad, 2
-                    q.dw, q.alpha, q.nbatch, q.ksplit = dw.data_ptr(), 1.0, 1, 0
+                    q = self._wgrad_params(x, cw, out.gptr, out.ld, Ho, Wo, dw.data_ptr(), stride=2)
                     if self.L.mrfa_conv2d_wgrad_stride_supported(C.byref(q)):
                         self._chk(self.L.mrfa_conv2d_wgrad_nhwc(self.s, C.byref(q)), "wgrad(stride 2)")
                         full = None
@@ -2125,8 +2028,7 @@ class Ctx:
                     full = full or self._zero_stuffed(out, x.H, x.W)
                     self._conv_dgrad(x, cw, full, False, None)
             self.tape.append(bwd)
-            if cw not in self.touched_convs:
-                self.touched_convs.append(cw)
+            self._touch(cw)
         return out, stats
 
     def _zero_stuffed(self, out: View, H: int, W: int) -> View:

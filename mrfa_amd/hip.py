@@ -222,6 +222,13 @@ EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 LN_SLOTS = 16          # MRFA_LN_SLOTS
 RESIZE_SUM_TERMS = 4   # MRFA_RESIZE_SUM_TERMS
 ABI_VERSION = 10       # MRFA_ABI_VERSION of include/mrfa_hip.h: the struct layouts above mirror THAT header; lib() refuses any other library
+# pack modes of mrfa_pack_conv_weight / mrfa_pack_conv_weights_multi: the table above mrfa_pack_conv_weight in include/mrfa_hip.h
+PACK_FWD, PACK_FWD_FLAT, PACK_DGRAD, PACK_DGRAD_FLAT = 0, 1, 2, 3        # fp32, chunked / flat-K
+PACK_FEWOUT, PACK_FEWIN = 5, 7                                           # fp32, the few-channel direct kernels
+PACK_FWD_SPLIT, PACK_DGRAD_SPLIT = 8, 9                                  # three bf16 pieces (batched entry point only, like all bf16 planes)
+PACK_FWD_PHASE, PACK_DGRAD_PHASE = 12, 13                                # three bf16 pieces of the 16 phase taps
+PACK_FWD_RNE, PACK_DGRAD_RNE = 14, 15                                    # one bf16 plane rounded to nearest even
+UNPACK_ACC, UNPACK_ACC_FEWOUT, UNPACK_OVERWRITE = 4, 6, 16               # gradient accumulator -> OIHW (+=); | UNPACK_OVERWRITE: (=)
 
 _lib = None
 
