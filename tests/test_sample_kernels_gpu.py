@@ -31,15 +31,11 @@ import torch
 
 from mrfa_amd import hip
 from tests import ref_sample as R
+from tests.kernel_check import CANARY, DEV, F64, NAN, U, Buf, check, note, report
 from tests.sample_grids import FLOWS, flow_grid, gs_grid
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-U = 2.0 ** -24
-NAN = float("nan")
-CANARY = -77.0
-F64 = torch.float64
 CAP = 256 * 16                                            # stream_grid (csrc/common.h): at most this many 256-thread workgroups, the rest grid-strides
 VEC_C = lambda c: c % 256 == 0 or c in (64, 128)
 
@@ -52,67 +48,6 @@ def steps(work_threads):
 
 def call(name, *args):
     hip.check(getattr(hip.lib(), name)(hip.stream_ptr(), *args), name)
-
-
-class Buf:
-    """values [rows, C] inside a [lead + groups * gstride] float buffer filled with `fill`: row r of group j starts at lead + j * gstride + r * ld"""
-
-    def __init__(self, vals, groups, ld, fill, lead=0, gap=0):
-        rows_all, Cc = vals.shape
-        self.rows, self.C, self.ld, self.groups, self.lead = rows_all // groups, Cc, ld, groups, lead
-        self.gstride = self.rows * ld + gap
-        self.flat = torch.full((lead + groups * self.gstride,), fill, dtype=torch.float32)
-        self.fill = fill
-        self._view(self.flat)[..., :Cc] = vals.view(groups, self.rows, Cc)
-        self.orig = self.flat.clone()
-        self.flat = self.flat.to(DEV)
-
-    def _view(self, flat):
-        return flat[self.lead:].view(self.groups, self.gstride)[:, :self.rows * self.ld].view(self.groups, self.rows, self.ld)
-
-    @property
-    def ptr(self):
-        return self.flat.data_ptr() + 4 * self.lead
-
-    def get(self):
-        """the values back ([rows_all, C], cpu) after asserting that nothing outside the slice changed"""
-        torch.cuda.synchronize()
-        now = self.flat.cpu()
-        a, b = now.clone(), self.orig.clone()
-        self._view(a)[..., :self.C] = 0
-        self._view(b)[..., :self.C] = 0
-        assert torch.equal(a.nan_to_num(nan=12345.0), b.nan_to_num(nan=12345.0)), "a kernel wrote outside its [.., :C] slice"
-        return self._view(now)[..., :self.C].reshape(-1, self.C).clone()
-
-
-def check(got, ref, bound, what, mask=None):
-    """|got - ref| <= bound element by element; returns max(err / bound)"""
-    got, ref, bound = got.to(F64).cpu(), ref.to(F64).cpu(), bound.to(F64).cpu()
-    assert got.shape == ref.shape == bound.shape, (what, got.shape, ref.shape, bound.shape)
-    if mask is not None:
-        m = mask.cpu().expand_as(got)
-        got, ref, bound = got[m], ref[m], bound[m]
-    assert torch.isfinite(got).all(), f"{what}: non-finite"
-    err = (got - ref).abs()
-    bad = err > bound
-    ratio = (err / bound.clamp(min=1e-300)).max().item() if err.numel() else 0.0
-    if bad.any():
-        i = int(bad.flatten().nonzero()[0])
-        raise AssertionError(f"{what}: {int(bad.sum())} of {err.numel()} elements beyond the bound; first at flat index {i}: got {got.flatten()[i].item():.9g} "
-                             f"ref {ref.flatten()[i].item():.9g} bound {bound.flatten()[i].item():.3e}; max err/bound {ratio:.3g}")
-    return ratio
-
-
-RATIOS = {}
-
-
-def note(test, what, ratio):
-    RATIOS[(test, what)] = max(RATIOS.get((test, what), 0.0), ratio)
-
-
-def report(test):
-    items = [(w, r) for (t, w), r in RATIOS.items() if t == test]
-    print(f"[sample] {test}: max err/bound " + "  ".join(f"{w} {r:.3f}" for w, r in items))
 
 
 # ================================================================================================================== grid_sample
