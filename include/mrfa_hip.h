@@ -45,8 +45,10 @@ const char* mrfa_last_error(void);
  *      groups > 1 the prologue vectors in_scale / in_shift of mrfa_conv_params are [groups][Cin] (only where mrfa_conv2d_groups_supported() says so:
  *      conv_lean.hip); all-taps multi-problem weight gradient of the same layers (wgrad_lean.hip, tuning key "wgrad_lean").
  *  10  bf16 activation STORAGE, first slice: mrfa_cast_bf16() and mrfa_grid_sample_bf16_fwd() (the source-feature cache of the animation loop; no struct
- *      changed: a version-9 client still works against this library, not the reverse).                                                                    */
-#define MRFA_ABI_VERSION 10
+ *      changed: a version-9 client still works against this library, not the reverse).
+ *  11  mrfa_corr_direct_fwd(): the correlation window computed from queries and keys where it is read, without the volumes (no struct changed: a version-10
+ *      client still works against this library, not the reverse).                                                                                         */
+#define MRFA_ABI_VERSION 11
 int mrfa_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -408,6 +410,16 @@ int mrfa_corr_lookup_fwd(void* stream, const float* vol0, const float* vol1, int
 int mrfa_corr_lookup_bwd(void* stream, const float* vol0, const float* vol1, int Hs, int Ws, const float* coords,
                          int ldc, long long Q, int radius, const float* dout, int lddo,
                          float* dvol0 /*+= atomics*/, float* dvol1, float* dcoords /*+=*/, int lddc);
+/* v11: the lookup WITHOUT the volumes (RAFT's alternate correlation; forward only, inference): out = mrfa_corr_lookup_fwd on
+ *   vol0[n Q + i, j] = scale * sum_c q[n, i, c] k0[n, j, c]   and   vol1[n Q + i, j] = scale * sum_c q[n, i, c] k1[n, j, c],   Q = h1 w1,
+ * of which only the (2r+2)^2 lattice points under each window are ever computed -- same taps, same selection rule (see K10: a sample at NaN, +-inf, <= -1 or
+ * >= W contributes nothing, an outside tap counts as 0), same blend with the weights of ix = cx / 2^lvl + (a - r) as the lookup evaluates it in fp32 (also
+ * where that sum rounds to an integer one past floor(cx / 2^lvl) + a - r).  q (N,h1,w1,D), k0 (N,Hs,Ws,D), k1 (N,Hs/2,Ws/2,D) fp32 NHWC views with leading
+ * dimensions ldq / ldk0 / ldk1; query image n reads key image n; coords and out as in mrfa_corr_lookup_fwd.  Each dot product is an fp32 FMA sum over D, then
+ * one multiplication by scale.  Every element offset is 64-bit.  Argument errors (no slow path): radius outside 0..3; Hs or Ws odd or < 2; D % 4 != 0;
+ * ldc < 2, ldo < 2 (2r+1)^2, ldq / ldk0 / ldk1 < D or not a multiple of 4; q / k0 / k1 not 16-byte aligned.                                              */
+int mrfa_corr_direct_fwd(void* stream, const float* q, int ldq, const float* k0, int ldk0, const float* k1, int ldk1, int N, int h1, int w1,
+                         int Hs, int Ws, int D, const float* coords, int ldc, int radius, float scale, float* out, int ldo);
 
 /* ------------------------------------------------------------------------------------------------------------
  * small layout / elementwise helpers                                                                            */

@@ -546,6 +546,99 @@ __global__ __launch_bounds__(256) void corr_lookup_kernel(const float* __restric
     }
 }
 
+// ---------------------------------------------------------------------------------------------- correlation window, computed where it is read
+// mrfa_corr_direct_fwd: corr_lookup_kernel<false> on the volumes vol_l[q, j] = scale * <q[q, :], k_l[n, j, :]> without the volumes.  One wave per query
+// pixel and pyramid level.  All (2r+1)^2 window elements share the fractional offsets, so the window's taps are the (2r+2)^2 <= 64 points of the integer
+// LATTICE anchored at (floor(cx inv) - r, floor(cy inv) - r); lattice point p = yj L + xi (L = 2r + 2, x fastest: consecutive points are consecutive key
+// pixels) ends up in lane p.  The dot products run eight lanes to a point: the eight lanes of a group read one 128-byte line of the point's key row per
+// step (a wave instruction = eight whole lines of eight neighbouring pixels), multiply with their slice of the query row -- held in registers for both
+// levels when D == 256 --, and a three-step butterfly sums the group; eight groups = eight points per round, (L^2 + 7) / 8 rounds.  A lattice point outside
+// the map reads a clamped address and is selected to 0, exactly what an outside tap counts as.  Lane e < (2r+1)^2 then blends its four taps out of the
+// lanes that hold them (ds_bpermute: no LDS is allocated, nothing to synchronise), with corr_lookup_kernel's own coordinate expression, selection rule and
+// weights (make_taps4).
+// fp32 rounding of `cx inv + (a - r)` can reach the next integer while cx inv is fractional: that element's floor is then lattice column a + 1 (still
+// inside: a + 1 <= 2r + 1) with fx = 0 exactly, and its far tap a + 2 may lie one past the lattice -- it is clamped onto the last column and weighs 0.
+// Queries are dealt out in contiguous runs: a wave walks `per` neighbouring pixels of a row (their windows overlap: L1), the four waves of a workgroup the
+// next runs, and every XCD one contiguous eighth of all queries (its L2 holds the key rows under them).
+template <int STEPS>       // 8: D == 256, the query slice in registers and every chunk present; 0: any D % 4 == 0, the query re-read per step (L1)
+__global__ __launch_bounds__(256) void corr_direct_kernel(const float* __restrict__ qp, int ldq, const float* __restrict__ k0, int ldk0,
+                                                         const float* __restrict__ k1, int ldk1, long long Q, long long QI, int Hs, int Ws, int D,
+                                                         const float* __restrict__ coords, int ldc, int radius, float scale, long long per,
+                                                         float* __restrict__ out, int ldo) {
+    const int lane = threadIdx.x & 63, grp = lane >> 3, sub = lane & 7;
+    const long long G = gridDim.x;
+    const long long lb = (long long)(blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);       // (gridDim.x is a multiple of 8)
+    const long long wave = lb * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const long long q_end = (wave + 1) * per < Q ? (wave + 1) * per : Q;
+    const int win = 2 * radius + 1, nwin = win * win, L = win + 1, npts = L * L;
+    const int a = lane / win, b = lane - a * win;
+    const bool active = lane < nwin;
+    for (long long q = wave * per; q < q_end; ++q) {
+        const long long n = q / QI;
+        const float cx = coords[(size_t)q * ldc], cy = coords[(size_t)q * ldc + 1];
+        const float* qrow = qp + (size_t)q * ldq + sub * 4;
+        f32x4 qreg[STEPS > 0 ? STEPS : 1];
+        if (STEPS > 0) {
+#pragma unroll
+            for (int s = 0; s < STEPS; ++s) qreg[s] = *reinterpret_cast<const f32x4*>(qrow + s * 32);
+        }
+#pragma unroll
+        for (int lvl = 0; lvl < 2; ++lvl) {
+            const int H = Hs >> lvl, W = Ws >> lvl;
+            const float inv = lvl == 0 ? 1.f : 0.5f;
+            const float* kb = lvl == 0 ? k0 : k1;
+            const int ldk = lvl == 0 ? ldk0 : ldk1;
+            // the anchor; a centre further out than the clamp has no live window element (NaN clamps to the lower end)
+            const int bx = (int)floorf(fminf(fmaxf(cx * inv, -(float)(radius + 2)), (float)(W + radius + 1))) - radius;
+            const int by = (int)floorf(fminf(fmaxf(cy * inv, -(float)(radius + 2)), (float)(H + radius + 1))) - radius;
+            float lat = 0.f;                                                               // lattice point `lane`
+            for (int p0 = 0; p0 < npts; p0 += 8) {
+                const int p = p0 + grp;
+                const int yj = p / L, xi = p - yj * L;
+                const int x = bx + xi, y = by + yj;
+                const bool ok = p < npts && x >= 0 && x < W && y >= 0 && y < H;
+                const int xc = x < 0 ? 0 : (x < W ? x : W - 1), yc = y < 0 ? 0 : (y < H ? y : H - 1);
+                const float* krow = kb + (((size_t)n * H + yc) * W + xc) * (size_t)ldk + sub * 4;
+                float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+                if (STEPS > 0) {
+                    f32x4 kv[STEPS > 0 ? STEPS : 1];
+#pragma unroll
+                    for (int s = 0; s < STEPS; ++s) kv[s] = *reinterpret_cast<const f32x4*>(krow + s * 32);
+#pragma unroll
+                    for (int s = 0; s < STEPS; ++s) {
+                        a0 = fmaf(qreg[s].x, kv[s].x, a0); a1 = fmaf(qreg[s].y, kv[s].y, a1);
+                        a2 = fmaf(qreg[s].z, kv[s].z, a2); a3 = fmaf(qreg[s].w, kv[s].w, a3);
+                    }
+                } else {
+                    for (int c = sub * 4; c < D; c += 32) {
+                        const f32x4 kv = *reinterpret_cast<const f32x4*>(krow + (c - sub * 4));
+                        const f32x4 qv = *reinterpret_cast<const f32x4*>(qrow + (c - sub * 4));
+                        a0 = fmaf(qv.x, kv.x, a0); a1 = fmaf(qv.y, kv.y, a1); a2 = fmaf(qv.z, kv.z, a2); a3 = fmaf(qv.w, kv.w, a3);
+                    }
+                }
+                float dot = (a0 + a1) + (a2 + a3);
+                dot += __shfl_xor(dot, 1, 64);
+                dot += __shfl_xor(dot, 2, 64);
+                dot += __shfl_xor(dot, 4, 64);                                             // every lane of the group holds the point's sum
+                const float v = ok ? dot * scale : 0.f;
+                const float mine = __shfl(v, sub * 8, 64);                                 // group `sub` of this round holds point p0 + sub
+                if (grp == (p0 >> 3)) lat = mine;                                          // lane = (p0 / 8) * 8 + sub = p0 + sub
+            }
+            const float ix = cx * inv + (float)(a - radius), iy = cy * inv + (float)(b - radius);
+            const Taps4 t = make_taps4(active ? ix : -2.f, iy, W, H);
+            const bool inr = t.ok00 || t.ok01 || t.ok10 || t.ok11;                         // (a live sample has a tap inside: ix in (-1, W))
+            const int x0 = inr ? (int)floorf(ix) : bx, y0 = inr ? (int)floorf(iy) : by;
+            const int li0 = min(max(x0 - bx, 0), L - 1), lj0 = min(max(y0 - by, 0), L - 1);
+            const int li1 = min(li0 + 1, L - 1), lj1 = min(lj0 + 1, L - 1);
+            const float l00 = __shfl(lat, lj0 * L + li0, 64), l01 = __shfl(lat, lj0 * L + li1, 64);
+            const float l10 = __shfl(lat, lj1 * L + li0, 64), l11 = __shfl(lat, lj1 * L + li1, 64);
+            const float v00 = t.ok00 ? l00 : 0.f, v01 = t.ok01 ? l01 : 0.f, v10 = t.ok10 ? l10 : 0.f, v11 = t.ok11 ? l11 : 0.f;
+            const float v = v00 * t.w00 + v01 * t.w01 + v10 * t.w10 + v11 * t.w11;
+            if (active) out[(size_t)q * ldo + lvl * nwin + lane] = v;
+        }
+    }
+}
+
 // Transform.transform_frame (model.py:44-48): F.grid_sample(frame, grid, padding_mode="reflection"), bilinear, align_corners=False, NCHW in and out, forward only
 // (the frame is data and the warp's parameters are random constants: nothing differentiates through it).  One thread per output pixel, all channels.
 __device__ __forceinline__ float reflect_coord(float v, float size) {
@@ -732,6 +825,31 @@ extern "C" int mrfa_corr_lookup_fwd(void* stream, const float* vol0, const float
     hipLaunchKernelGGL((corr_lookup_kernel<false>), dim3(stream_grid(Q * 64, 256)), dim3(256), 0, (hipStream_t)stream, vol0, vol1, Hs, Ws,
                        coords, ldc, Q, radius, out, ldo, nullptr, 0, nullptr, nullptr, nullptr, 0);
     MRFA_CHECK_LAUNCH("corr_lookup_fwd");
+    return 0;
+}
+
+extern "C" int mrfa_corr_direct_fwd(void* stream, const float* q, int ldq, const float* k0, int ldk0, const float* k1, int ldk1, int N, int h1, int w1,
+                                    int Hs, int Ws, int D, const float* coords, int ldc, int radius, float scale, float* out, int ldo) {
+    MRFA_CHECK_ARG(radius >= 0 && radius <= 3, "corr_direct: the window's lattice must fit one wave (0 <= radius <= 3, got %d)", radius);
+    MRFA_CHECK_ARG(q && k0 && k1 && coords && out && N > 0 && h1 > 0 && w1 > 0 && D > 0, "corr_direct_fwd: bad args (null pointer or non-positive size; "
+                   "N %d, h1 %d, w1 %d, D %d)", N, h1, w1, D);
+    MRFA_CHECK_ARG(Hs >= 2 && Ws >= 2 && Hs % 2 == 0 && Ws % 2 == 0, "corr_direct_fwd: Hs and Ws must be even and >= 2 (the pooled level is Hs/2 x Ws/2; "
+                   "Hs %d, Ws %d)", Hs, Ws);
+    MRFA_CHECK_ARG(ldc >= 2 && ldo >= 2 * (2 * radius + 1) * (2 * radius + 1) && ldq >= D && ldk0 >= D && ldk1 >= D,
+                   "corr_direct_fwd: a leading dimension is below its channel count (ldc >= 2, ldo >= 2 (2r+1)^2, ldq / ldk0 / ldk1 >= D; ldc %d, ldo %d, "
+                   "ldq %d, ldk0 %d, ldk1 %d, D %d, radius %d)", ldc, ldo, ldq, ldk0, ldk1, D, radius);
+    MRFA_CHECK_ARG(D % 4 == 0 && ldq % 4 == 0 && ldk0 % 4 == 0 && ldk1 % 4 == 0 && aligned16(q) && aligned16(k0) && aligned16(k1),
+                   "corr_direct_fwd: needs D %% 4 == 0, ldq / ldk0 / ldk1 %% 4 == 0 and 16-byte aligned q / k0 / k1 (16-byte loads; D %d, ldq %d, ldk0 %d, "
+                   "ldk1 %d)", D, ldq, ldk0, ldk1);
+    const long long QI = (long long)h1 * w1, Q = (long long)N * QI;
+    long long blocks = ((Q + 3) / 4 + 7) / 8 * 8;                      // four waves (queries) per workgroup, a multiple of 8 workgroups (XCD walk)
+    if (blocks > 2048) blocks = 2048;                                  // 256 CUs x 8: beyond that a wave walks a longer run of neighbouring queries
+    const long long per = (Q + blocks * 4 - 1) / (blocks * 4);
+#define CDK(S) hipLaunchKernelGGL((corr_direct_kernel<S>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, q, ldq, k0, ldk0, k1, ldk1, Q, QI, \
+                                  Hs, Ws, D, coords, ldc, radius, scale, per, out, ldo)
+    if (D == 256) CDK(8); else CDK(0);
+#undef CDK
+    MRFA_CHECK_LAUNCH("corr_direct_fwd");
     return 0;
 }
 

@@ -167,6 +167,7 @@ _SIGNATURES = {
     "mrfa_resize_sum_multi_bwd": ([_V, C.POINTER(ResizeSumDesc), _I], C.c_int),
     "mrfa_corr_lookup_fwd": ([_V, _V, _V, _I, _I, _V, _I, _L, _I, _V, _I], C.c_int),
     "mrfa_corr_lookup_bwd": ([_V, _V, _V, _I, _I, _V, _I, _L, _I, _V, _I, _V, _V, _V, _I], C.c_int),
+    "mrfa_corr_direct_fwd": ([_V, _V, _I, _V, _I, _V, _I, _I, _I, _I, _I, _I, _I, _V, _I, _I, _F, _V, _I], C.c_int),
     "mrfa_nchw_to_nhwc": ([_V, _V, _V, _I, _I, _I, _I, _I, _I], C.c_int),
     "mrfa_nhwc_to_nchw": ([_V, _V, _I, _V, _I, _I, _I, _I, _I], C.c_int),
     "mrfa_avgpool2_fwd": ([_V, _V, _I, _I, _I, _I, _I, _V, _I], C.c_int),
@@ -221,7 +222,7 @@ _SIGNATURES = {
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 LN_SLOTS = 16          # MRFA_LN_SLOTS
 RESIZE_SUM_TERMS = 4   # MRFA_RESIZE_SUM_TERMS
-ABI_VERSION = 10       # MRFA_ABI_VERSION of include/mrfa_hip.h: the struct layouts above mirror THAT header; lib() refuses any other library
+ABI_VERSION = 11       # MRFA_ABI_VERSION of include/mrfa_hip.h: the struct layouts above mirror THAT header; lib() refuses any other library
 # pack modes of mrfa_pack_conv_weight / mrfa_pack_conv_weights_multi: the table above mrfa_pack_conv_weight in include/mrfa_hip.h
 PACK_FWD, PACK_FWD_FLAT, PACK_DGRAD, PACK_DGRAD_FLAT = 0, 1, 2, 3        # fp32, chunked / flat-K
 PACK_FEWOUT, PACK_FEWIN = 5, 7                                           # fp32, the few-channel direct kernels

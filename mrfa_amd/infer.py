@@ -9,6 +9,8 @@ from typing import Optional
 import torch
 from torch import nn
 
+from .modules.raft import check_corr
+
 
 def _check_cache_dtype(cache_dtype):
     if cache_dtype not in (torch.float32, torch.bfloat16):
@@ -17,13 +19,15 @@ def _check_cache_dtype(cache_dtype):
 
 
 class Animator:
-    def __init__(self, model: nn.Module, graph: bool = False, cache_dtype: torch.dtype = torch.float32):
+    def __init__(self, model: nn.Module, graph: bool = False, cache_dtype: torch.dtype = torch.float32, corr: str = "volume"):
         """model: mrfa_amd.train.HotPath or mrfa_amd.modules.model.MRFA (attributes encoder / dense_motion / decoder / down).
         cache_dtype: storage of the cached source feature pyramid (RaftFlow.encode_source(feature_dtype=)); torch.bfloat16 halves what the cache holds
-        and what the per-frame warps gather, at the cost of one rounding of the source features"""
+        and what the per-frame warps gather, at the cost of one rounding of the source features.
+        corr: RaftFlow.forward(corr=): "direct" correlates each looked-up window where it is read and builds no correlation volume per frame"""
         self.m = model.eval()
         self.use_graph = graph
         self.cache_dtype = _check_cache_dtype(cache_dtype)
+        self.corr = check_corr(corr)
         self.source = None
         self._g: Optional[torch.cuda.CUDAGraph] = None
 
@@ -41,7 +45,7 @@ class Animator:
         m = self.m
         kp_d = m.encoder(driving)
         dm = m.dense_motion(self.source, kp_d, self.kp_s)
-        out, _, _ = m.decoder(self.kp_s["kp"], kp_d["kp"], dm, img=self.img_down, img_full=self.source, source_cache=self.cache)
+        out, _, _ = m.decoder(self.kp_s["kp"], kp_d["kp"], dm, img=self.img_down, img_full=self.source, source_cache=self.cache, corr=self.corr)
         return out
 
     @torch.no_grad()
@@ -121,11 +125,11 @@ def psnr(img1: torch.Tensor, img2: torch.Tensor):
 
 
 @torch.no_grad()
-def reconstruction(model: nn.Module, video: torch.Tensor, graph: bool = False, cache_dtype: torch.dtype = torch.float32):
+def reconstruction(model: nn.Module, video: torch.Tensor, graph: bool = False, cache_dtype: torch.dtype = torch.float32, corr: str = "volume"):
     """The reference's reconstruction loop (reconstruction.py:52-70) on one clip: source = frame 0, driving = every frame t,
     metrics mean|out - driving| and PSNR per frame.  video: (B,3,T,H,W) in [0,1].  The source is fixed for the whole clip, so
     the source half of the path is computed once (Animator).  Returns {'prediction': (B,3,T,H,W), 'l1': [T], 'psnr': [T]}."""
-    anim = Animator(model, graph=graph, cache_dtype=cache_dtype)
+    anim = Animator(model, graph=graph, cache_dtype=cache_dtype, corr=corr)
     anim.set_source(video[:, :, 0].contiguous())
     preds, l1, ps = [], [], []
     for t in range(video.shape[2]):
@@ -139,10 +143,11 @@ def reconstruction(model: nn.Module, video: torch.Tensor, graph: bool = False, c
 
 @torch.no_grad()
 def make_animation(model: nn.Module, source: torch.Tensor, driving_video: torch.Tensor, relative: bool = True,
-                   adapt_movement_scale: bool = False, graph: bool = False, cache_dtype: torch.dtype = torch.float32):
+                   adapt_movement_scale: bool = False, graph: bool = False, cache_dtype: torch.dtype = torch.float32, corr: str = "volume"):
     """demo.py:47-73 / animate_ddp.py:88-105: animate ONE source by the motion of a driving clip (B,3,T,H,W); with
     relative=True the driving keypoints go through normalize_kp against the first driving frame.  Returns (B,3,T,H,W)."""
     _check_cache_dtype(cache_dtype)
+    check_corr(corr)
     m = model.eval()
     kp_s = m.encoder(source)
     img_down = m.down(source)
@@ -154,6 +159,6 @@ def make_animation(model: nn.Module, source: torch.Tensor, driving_video: torch.
         kp_n = normalize_kp(kp_s, kp_d, kp_init, adapt_movement_scale=adapt_movement_scale, use_relative_movement=relative,
                             use_relative_jacobian=relative)
         dm = m.dense_motion(source, kp_n, kp_s)
-        out, _, _ = m.decoder(kp_s["kp"], kp_n["kp"], dm, img=img_down, img_full=source, source_cache=cache)
+        out, _, _ = m.decoder(kp_s["kp"], kp_n["kp"], dm, img=img_down, img_full=source, source_cache=cache, corr=corr)
         outs.append(out.clone())
     return torch.stack(outs, dim=2)

@@ -168,6 +168,13 @@ class _CorrVolume:
         self.dvol0 = self.dvol1 = None
 
 
+def check_corr(corr):
+    """the one place that knows RaftFlow.forward(corr=)'s legal values (mrfa_amd.infer checks its own arguments with it)"""
+    if corr not in ("volume", "direct"):
+        raise ValueError(f'corr must be "volume" or "direct", not {corr!r}')
+    return corr
+
+
 _GRID_CONSTS: dict = {}
 
 
@@ -253,7 +260,7 @@ class RaftFlow(nn.Module):
         e.from_nchw(img, out=in_s.slice(K, K + img.shape[1]))
         return in_s
 
-    def _program(self, e: Ctx, kp_s, kp_d, deformation, occlusion, img, img_full, cache=None):
+    def _program(self, e: Ctx, kp_s, kp_d, deformation, occlusion, img, img_full, cache=None, corr="volume"):
         gen = self.generator
         if cache is not None:
             assert not e.record and cache["shape"] == tuple(img_full.shape), "source cache: inference only, same source batch"
@@ -308,7 +315,8 @@ class RaftFlow(nn.Module):
         q_levels = {base: q_d}
         for i in range(base - 1, -1, -1):                                       # pooled queries == volume pooled over driving dims
             q_levels[i] = e.avgpool2(q_levels[i + 1])
-        vols = {i: _CorrVolume(e, q_levels[i], k_s, k_pool, self.scale) for i in range(base + 1)}
+        # corr="direct": no volumes -- every lookup below computes its window's lattice from q_levels[.] and k_s / pooled k_s (mrfa_corr_direct_fwd)
+        vols = {i: _CorrVolume(e, q_levels[i], k_s, k_pool, self.scale) for i in range(base + 1)} if corr == "volume" else None
 
         # ---- prior initialisation (raft.py:189-206)
         with e.fused_resizes():                                                 # init_flow = (h-1)/2 (deform + 1) - identity grid, one launch
@@ -329,15 +337,18 @@ class RaftFlow(nn.Module):
             r = r0 * (2 ** i)
             f = feature[i]
             if i < base:
-                cscale, vol, rq = float(2 ** (base - i)), vols[i], r
+                cscale, lv, rq = float(2 ** (base - i)), i, r
                 flow_q = flow
             else:
-                cscale, vol, rq = 1.0, vols[base], h
+                cscale, lv, rq = 1.0, base, h
                 flow_q = e.resize(flow, h, w, mul=0.5 ** (i - base)) if i > base else flow
             with e.fused_resizes():                                             # coords = cscale (flow + identity grid), one launch
                 coords = e.copy(flow_q, mul=cscale)
                 e.copy(_grid_const(e, b, rq, rq, cscale, 0.0, img_full), out=coords, acc=True, nograd=True)
-            cfeat = e.corr_lookup(vol.vol0, vol.vol1, vol.dvols, h, w, coords)
+            if vols is not None:
+                cfeat = e.corr_lookup(vols[lv].vol0, vols[lv].vol1, vols[lv].dvols, h, w, coords)
+            else:
+                cfeat = e.corr_direct(q_levels[lv], k_s, k_pool, coords, self.scale)
             if i > base:
                 cfeat = e.resize(cfeat, r, r)
             inp = e.new(b, r, r, 256)
@@ -388,12 +399,23 @@ class RaftFlow(nn.Module):
         seed = ((lambda g: e.seed_grad_nchw(out, g)), (lambda g: e.seed_grad_nchw(warp_img, g)), None)
         return outs, seed, in_grads
 
-    def forward(self, kp_s, kp_d, dense_motion, img, img_full, source_cache=None):
-        """source_cache (extension, inference only): the result of encode_source(kp_s, img, img_full) for this source"""
+    def forward(self, kp_s, kp_d, dense_motion, img, img_full, source_cache=None, corr="volume"):
+        """source_cache (extension, inference only): the result of encode_source(kp_s, img, img_full) for this source.
+        corr (extension): "volume" builds the all-pairs correlation volumes of every query level and looks the windows up in them (the reference's program);
+        "direct" (inference only: it has no backward) computes each looked-up window from the queries and keys instead and builds no volume -- the same
+        values up to fp32 summation order, none of the volumes' memory."""
+        if check_corr(corr) == "direct":
+            if self.training:
+                raise ValueError('corr="direct" is an inference mode (the direct correlation kernel has no backward): call eval() first, training keeps the volumes')
+            ins_grad = (kp_s, kp_d, dense_motion['deformation'], dense_motion['occlusion'])
+            if torch.is_grad_enabled() and any(t.requires_grad for t in (*self.parameters(), *ins_grad)):
+                raise ValueError('corr="direct" has no backward: run it under torch.no_grad() (gradients are enabled and a parameter or input requires one)')
         if img is None:
             raise ValueError("RaftFlow.forward needs `img` (the 1/4-resolution source); the reference crashes on None too "
                              "(raft.py:144-145 uses a commented-out self.down)")
         ins = [kp_s, kp_d, dense_motion['deformation'], dense_motion['occlusion'], img, img_full]
-        program = self._program if source_cache is None else functools.partial(self._program, cache=source_cache)
+        program = self._program
+        if source_cache is not None or corr != "volume":
+            program = functools.partial(self._program, cache=source_cache, corr=corr)
         out, warp_img, strip = run_program(self, program, ins)
         return out, warp_img, strip

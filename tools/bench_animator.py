@@ -1,5 +1,16 @@
-"""Per-frame time of the streaming animation loop (source-side work cached) vs the full per-pair forward, hipGraph replays."""
+"""Per-frame time of the streaming animation loop (source-side work cached) vs the full per-pair forward, hipGraph replays.
+
+    python tools/bench_animator.py                                  # 256^2, B = 1 and 8, the volume correlation (the original report)
+    python tools/bench_animator.py --corr direct                    # the same with RaftFlow.forward(corr="direct") in the Animator
+    python tools/bench_animator.py --corr volume direct --size 512 --batch 1 --rounds 5
+                                                                    # alternating rounds of both modes in ONE process: median and spread per mode
+    python tools/bench_animator.py --corr volume direct --raft-forward --size 512 --batch 4
+                                                                    # the RaftFlow forward of bench.py's 512^2 inference configuration, graphed
+"""
+import argparse
+import copy
 import os
+import statistics
 import sys
 import time
 
@@ -11,26 +22,104 @@ from mrfa_amd.infer import Animator  # noqa: E402
 from mrfa_amd.train import VOX1, HotPath  # noqa: E402
 from mrfa_amd.utils.prng import det_uniform, fill_state_dict  # noqa: E402
 
+ap = argparse.ArgumentParser()
+ap.add_argument("--corr", nargs="+", choices=("volume", "direct"), default=["volume"], help="RaftFlow correlation mode(s); two modes alternate round by round")
+ap.add_argument("--size", type=int, default=256)
+ap.add_argument("--batch", type=int, nargs="+", default=[1, 8])
+ap.add_argument("--rounds", type=int, default=1, help="timed rounds per mode (20 frames each); > 1 prints median and min-max")
+ap.add_argument("--raft-forward", action="store_true", help="time the graphed RaftFlow forward on fixed prior inputs instead of the Animator frame")
+ap.add_argument("--no-graph", action="store_true")
+a = ap.parse_args()
+
 dev = torch.device("cuda", 0)
-model = HotPath(VOX1)
-for pfx, mod in (("encoder.", model.encoder), ("dense_motion.", model.dense_motion), ("decoder.", model.decoder)):
-    mod.load_state_dict(fill_state_dict(mod.state_dict(), tag=pfx))
-model.to(dev).eval()
-for B in (1, 8):
-    src = det_uniform("ba/src", (B, 3, 256, 256), 0, 1).to(dev)
-    drv = det_uniform("ba/drv", (B, 3, 256, 256), 0, 1).to(dev)
-    gf = GraphedForward(model, src, drv)
-    an = Animator(model, graph=True)
-    an.set_source(src)
-    res = {}
-    for name, fn in (("full forward", lambda: gf(src, drv)), ("animator frame", lambda: an(drv))):
-        for _ in range(3):
-            fn()
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        for _ in range(20):
-            fn()
-        torch.cuda.synchronize()
-        res[name] = (time.perf_counter() - t) / 20 * 1e3
-    print(f"B={B}: full forward {res['full forward']:.2f} ms, animator frame {res['animator frame']:.2f} ms "
-          f"({B / res['animator frame'] * 1e3:.0f} frames/s)")
+cfg = copy.deepcopy(VOX1)
+cfg["raft_flow"]["size"] = a.size
+
+
+def timed(fn, n=20):
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    for _ in range(n):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t) / n * 1e3
+
+
+def summary(ts):
+    return f"{statistics.median(ts):.3f} ms" + (f" (median of {len(ts)}, {min(ts):.3f} - {max(ts):.3f})" if len(ts) > 1 else "")
+
+
+def raft_forward_steps(B):
+    """the RaftFlow forward of bench.py --inference (same weights, same inputs), one step function per correlation mode"""
+    from mrfa_amd.modules import RaftFlow
+    size, h = a.size, a.size // 4
+    rf = RaftFlow(**cfg["raft_flow"])
+    sd = fill_state_dict(rf.state_dict(), tag="decoder.")
+    for k in list(sd):
+        if k.endswith(("refine.conv2.weight", "refine.convo2.weight")):
+            sd[k] = sd[k] * 0.3
+    rf.load_state_dict(sd)
+    rf.to(dev).eval()
+    img_full = det_uniform("c5/img", (B, 3, size, size), 0, 1).to(dev)
+    img = torch.nn.functional.avg_pool2d(img_full, 4)
+    kp_s, kp_d = det_uniform("c5/ks", (B, 10, 2), -0.8, 0.8).to(dev), det_uniform("c5/kd", (B, 10, 2), -0.8, 0.8).to(dev)
+    ys, xs = torch.meshgrid(torch.linspace(-1, 1, h), torch.linspace(-1, 1, h), indexing="ij")
+    deform = (torch.stack([xs, ys], dim=-1)[None].expand(B, h, h, 2) + det_uniform("c5/d", (B, h, h, 2), -0.1, 0.1)).contiguous().to(dev)
+    dm = {"deformation": deform, "occlusion": det_uniform("c5/o", (B, 1, h, h), -2, 2).to(dev)}
+
+    class _Fwd(torch.nn.Module):
+        def __init__(self, corr):
+            super().__init__()
+            self.rf, self.corr = rf, corr
+
+        def forward(self, full, quarter):
+            return self.rf(kp_s, kp_d, dm, quarter, full, corr=self.corr)[0]
+    steps, outs = {}, {}
+    with torch.no_grad():
+        for corr in a.corr:
+            m = _Fwd(corr).eval()
+            if a.no_graph:
+                steps[corr] = lambda m=m: m(img_full, img)
+            else:
+                gf = GraphedForward(m, img_full, img)
+                steps[corr] = lambda gf=gf: gf(gf.src, gf.drv)
+            outs[corr] = steps[corr]().clone()
+    if len(outs) == 2:
+        d = (outs["volume"] - outs["direct"]).abs()
+        print(f"  direct vs volume output: max |diff| {d.max().item():.3e} mean {d.mean().item():.3e}")
+    return steps
+
+
+def animator_steps(B):
+    model = HotPath(cfg)
+    for pfx, mod in (("encoder.", model.encoder), ("dense_motion.", model.dense_motion), ("decoder.", model.decoder)):
+        mod.load_state_dict(fill_state_dict(mod.state_dict(), tag=pfx))
+    model.to(dev).eval()
+    src = det_uniform("ba/src", (B, 3, a.size, a.size), 0, 1).to(dev)
+    drv = det_uniform("ba/drv", (B, 3, a.size, a.size), 0, 1).to(dev)
+    steps = {}
+    if a.corr == ["volume"] and a.rounds == 1 and not a.no_graph:
+        gf = GraphedForward(model, src, drv)
+        steps["full forward"] = lambda: gf(src, drv)
+    for corr in a.corr:
+        an = Animator(model, graph=not a.no_graph, corr=corr)
+        an.set_source(src)
+        steps[corr] = lambda an=an: an(drv)
+    return steps
+
+
+for B in a.batch:
+    with torch.no_grad():
+        steps = raft_forward_steps(B) if a.raft_forward else animator_steps(B)
+        times = {k: [] for k in steps}
+        for fn in steps.values():
+            for _ in range(3):
+                fn()
+        for _ in range(a.rounds):
+            for k, fn in steps.items():                       # the modes alternate round by round: same box, same minute
+                times[k].append(timed(fn))
+    what = "RaftFlow forward" if a.raft_forward else "animator frame"
+    for k, ts in times.items():
+        label = k if k == "full forward" else f"{what} corr={k}"
+        extra = f" ({B / statistics.median(ts) * 1e3:.0f} frames/s)" if k != "full forward" else ""
+        print(f"{a.size}^2 B={B}: {label} {summary(ts)}{extra}")
