@@ -47,7 +47,9 @@ const char* mrfa_last_error(void);
  *  10  bf16 activation STORAGE, first slice: mrfa_cast_bf16() and mrfa_grid_sample_bf16_fwd() (the source-feature cache of the animation loop; no struct
  *      changed: a version-9 client still works against this library, not the reverse).
  *  11  mrfa_corr_direct_fwd(): the correlation window computed from queries and keys where it is read, without the volumes (no struct changed: a version-10
- *      client still works against this library, not the reverse).                                                                                         */
+ *      client still works against this library, not the reverse).
+ *      Still 11: mrfa_corr_direct_rep_fwd() (k_rep consecutive query images read one key image: a clip of one source) is additive -- no struct and no existing
+ *      entry changed, so the number stays; a client that wants it looks the symbol up and treats its absence as an older version-11 library.             */
 #define MRFA_ABI_VERSION 11
 int mrfa_version(void);
 
@@ -420,6 +422,11 @@ int mrfa_corr_lookup_bwd(void* stream, const float* vol0, const float* vol1, int
  * ldc < 2, ldo < 2 (2r+1)^2, ldq / ldk0 / ldk1 < D or not a multiple of 4; q / k0 / k1 not 16-byte aligned.                                              */
 int mrfa_corr_direct_fwd(void* stream, const float* q, int ldq, const float* k0, int ldk0, const float* k1, int ldk1, int N, int h1, int w1,
                          int Hs, int Ws, int D, const float* coords, int ldc, int radius, float scale, float* out, int ldo);
+/* v11, additive: mrfa_corr_direct_fwd in every word except that query image n reads key image n / k_rep (the frames of one source are consecutive: the
+ * convention of mrfa_grid_sample_fwd's in_rep); k0 and k1 hold N / k_rep images.  Same kernels, same arithmetic in the same order: the output equals, bit
+ * for bit, mrfa_corr_direct_fwd on keys repeated k_rep times.  Further argument errors: k_rep < 1, N % k_rep != 0.  An argument error leaves out untouched. */
+int mrfa_corr_direct_rep_fwd(void* stream, const float* q, int ldq, const float* k0, int ldk0, const float* k1, int ldk1, int N, int k_rep, int h1, int w1,
+                             int Hs, int Ws, int D, const float* coords, int ldc, int radius, float scale, float* out, int ldo);
 
 /* ------------------------------------------------------------------------------------------------------------
  * small layout / elementwise helpers                                                                            */

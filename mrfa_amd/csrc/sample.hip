@@ -560,9 +560,11 @@ __global__ __launch_bounds__(256) void corr_lookup_kernel(const float* __restric
 // inside: a + 1 <= 2r + 1) with fx = 0 exactly, and its far tap a + 2 may lie one past the lattice -- it is clamped onto the last column and weighs 0.
 // Queries are dealt out in contiguous runs: a wave walks `per` neighbouring pixels of a row (their windows overlap: L1), the four waves of a workgroup the
 // next runs, and every XCD one contiguous eighth of all queries (its L2 holds the key rows under them).
+// QK = queries per KEY image: h1 w1 where every query image has its own keys, k_rep h1 w1 where k_rep consecutive query images share one
+// (mrfa_corr_direct_rep_fwd) -- the only place the two entry points differ is which key image `q / QK` names.
 template <int STEPS>       // 8: D == 256, the query slice in registers and every chunk present; 0: any D % 4 == 0, the query re-read per step (L1)
 __global__ __launch_bounds__(256) void corr_direct_kernel(const float* __restrict__ qp, int ldq, const float* __restrict__ k0, int ldk0,
-                                                         const float* __restrict__ k1, int ldk1, long long Q, long long QI, int Hs, int Ws, int D,
+                                                         const float* __restrict__ k1, int ldk1, long long Q, long long QK, int Hs, int Ws, int D,
                                                          const float* __restrict__ coords, int ldc, int radius, float scale, long long per,
                                                          float* __restrict__ out, int ldo) {
     const int lane = threadIdx.x & 63, grp = lane >> 3, sub = lane & 7;
@@ -574,7 +576,7 @@ __global__ __launch_bounds__(256) void corr_direct_kernel(const float* __restric
     const int a = lane / win, b = lane - a * win;
     const bool active = lane < nwin;
     for (long long q = wave * per; q < q_end; ++q) {
-        const long long n = q / QI;
+        const long long n = q / QK;                                                        // key image
         const float cx = coords[(size_t)q * ldc], cy = coords[(size_t)q * ldc + 1];
         const float* qrow = qp + (size_t)q * ldq + sub * 4;
         f32x4 qreg[STEPS > 0 ? STEPS : 1];
@@ -828,8 +830,9 @@ extern "C" int mrfa_corr_lookup_fwd(void* stream, const float* vol0, const float
     return 0;
 }
 
-extern "C" int mrfa_corr_direct_fwd(void* stream, const float* q, int ldq, const float* k0, int ldk0, const float* k1, int ldk1, int N, int h1, int w1,
-                                    int Hs, int Ws, int D, const float* coords, int ldc, int radius, float scale, float* out, int ldo) {
+// both entry points of the direct correlation: k_rep consecutive query images read one key image (k_rep == 1: mrfa_corr_direct_fwd, word for word)
+static int corr_direct_launch(void* stream, const float* q, int ldq, const float* k0, int ldk0, const float* k1, int ldk1, int N, int k_rep, int h1, int w1,
+                              int Hs, int Ws, int D, const float* coords, int ldc, int radius, float scale, float* out, int ldo) {
     MRFA_CHECK_ARG(radius >= 0 && radius <= 3, "corr_direct: the window's lattice must fit one wave (0 <= radius <= 3, got %d)", radius);
     MRFA_CHECK_ARG(q && k0 && k1 && coords && out && N > 0 && h1 > 0 && w1 > 0 && D > 0, "corr_direct_fwd: bad args (null pointer or non-positive size; "
                    "N %d, h1 %d, w1 %d, D %d)", N, h1, w1, D);
@@ -841,16 +844,28 @@ extern "C" int mrfa_corr_direct_fwd(void* stream, const float* q, int ldq, const
     MRFA_CHECK_ARG(D % 4 == 0 && ldq % 4 == 0 && ldk0 % 4 == 0 && ldk1 % 4 == 0 && aligned16(q) && aligned16(k0) && aligned16(k1),
                    "corr_direct_fwd: needs D %% 4 == 0, ldq / ldk0 / ldk1 %% 4 == 0 and 16-byte aligned q / k0 / k1 (16-byte loads; D %d, ldq %d, ldk0 %d, "
                    "ldk1 %d)", D, ldq, ldk0, ldk1);
-    const long long QI = (long long)h1 * w1, Q = (long long)N * QI;
+    const long long QI = (long long)h1 * w1, Q = (long long)N * QI, QK = QI * k_rep;
     long long blocks = ((Q + 3) / 4 + 7) / 8 * 8;                      // four waves (queries) per workgroup, a multiple of 8 workgroups (XCD walk)
     if (blocks > 2048) blocks = 2048;                                  // 256 CUs x 8: beyond that a wave walks a longer run of neighbouring queries
     const long long per = (Q + blocks * 4 - 1) / (blocks * 4);
-#define CDK(S) hipLaunchKernelGGL((corr_direct_kernel<S>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, q, ldq, k0, ldk0, k1, ldk1, Q, QI, \
+#define CDK(S) hipLaunchKernelGGL((corr_direct_kernel<S>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, q, ldq, k0, ldk0, k1, ldk1, Q, QK, \
                                   Hs, Ws, D, coords, ldc, radius, scale, per, out, ldo)
     if (D == 256) CDK(8); else CDK(0);
 #undef CDK
     MRFA_CHECK_LAUNCH("corr_direct_fwd");
     return 0;
+}
+
+extern "C" int mrfa_corr_direct_fwd(void* stream, const float* q, int ldq, const float* k0, int ldk0, const float* k1, int ldk1, int N, int h1, int w1,
+                                    int Hs, int Ws, int D, const float* coords, int ldc, int radius, float scale, float* out, int ldo) {
+    return corr_direct_launch(stream, q, ldq, k0, ldk0, k1, ldk1, N, 1, h1, w1, Hs, Ws, D, coords, ldc, radius, scale, out, ldo);
+}
+
+extern "C" int mrfa_corr_direct_rep_fwd(void* stream, const float* q, int ldq, const float* k0, int ldk0, const float* k1, int ldk1, int N, int k_rep,
+                                        int h1, int w1, int Hs, int Ws, int D, const float* coords, int ldc, int radius, float scale, float* out, int ldo) {
+    MRFA_CHECK_ARG(k_rep >= 1 && N % k_rep == 0, "corr_direct_rep_fwd: k_rep consecutive query images share a key image, so k_rep >= 1 must divide N "
+                   "(N %d, k_rep %d)", N, k_rep);
+    return corr_direct_launch(stream, q, ldq, k0, ldk0, k1, ldk1, N, k_rep, h1, w1, Hs, Ws, D, coords, ldc, radius, scale, out, ldo);
 }
 
 extern "C" int mrfa_corr_lookup_bwd(void* stream, const float* vol0, const float* vol1, int Hs, int Ws, const float* coords, int ldc,

@@ -1746,17 +1746,23 @@ class Ctx:
             self.tape.append(bwd)
         return out
 
-    def corr_direct(self, q: View, k0: View, k1: View, coords: View, scale: float, radius: int = 3, out: Optional[View] = None) -> View:
-        """corr_lookup on the volumes scale * q.k0^T / scale * q.k1^T without building them: q (N,h1,w1,D) queries, k0 (N,Hs,Ws,D) keys, k1 their 2x2
-        pooling, coords (N,h1,w1,2).  Inference only: the kernel has no backward."""
+    def corr_direct(self, q: View, k0: View, k1: View, coords: View, scale: float, radius: int = 3, out: Optional[View] = None, k_rep: int = 1) -> View:
+        """corr_lookup on the volumes scale * q.k0^T / scale * q.k1^T without building them: q (N,h1,w1,D) queries, k0 (N / k_rep,Hs,Ws,D) keys, k1 their
+        2x2 pooling, coords (N,h1,w1,2).  k_rep > 1: query image n reads key image n // k_rep (the frames of one source, consecutive).
+        Inference only: the kernel has no backward."""
         if self.record:
             raise RuntimeError("Ctx.corr_direct: the direct correlation has no backward, not legal in a recording (training) program")
         assert coords.C == 2 and (coords.N, coords.H, coords.W) == (q.N, q.H, q.W), "corr_direct: one coordinate pair per query pixel"
-        assert k0.N == k1.N == q.N and k0.C == k1.C == q.C and (k1.H, k1.W) == (k0.H // 2, k0.W // 2), "corr_direct: key image n for query image n, k1 = pooled k0"
+        assert k_rep >= 1 and q.N == k0.N * k_rep, f"corr_direct: key image n // k_rep for query image n ({q.N} query images, {k0.N} key images, k_rep {k_rep})"
+        assert k0.N == k1.N and k0.C == k1.C == q.C and (k1.H, k1.W) == (k0.H // 2, k0.W // 2), "corr_direct: k1 = pooled k0, the queries' channels"
         nwin = (2 * radius + 1) ** 2
         out = out or self.new(q.N, q.H, q.W, 2 * nwin, pad32=True)
-        self._chk(self.L.mrfa_corr_direct_fwd(self.s, q.ptr, q.ld, k0.ptr, k0.ld, k1.ptr, k1.ld, q.N, q.H, q.W, k0.H, k0.W, q.C, coords.ptr, coords.ld,
-                                              radius, scale, out.ptr, out.ld), "corr_direct_fwd")
+        if k_rep == 1:
+            self._chk(self.L.mrfa_corr_direct_fwd(self.s, q.ptr, q.ld, k0.ptr, k0.ld, k1.ptr, k1.ld, q.N, q.H, q.W, k0.H, k0.W, q.C, coords.ptr, coords.ld,
+                                                  radius, scale, out.ptr, out.ld), "corr_direct_fwd")
+        else:
+            self._chk(self.L.mrfa_corr_direct_rep_fwd(self.s, q.ptr, q.ld, k0.ptr, k0.ld, k1.ptr, k1.ld, q.N, k_rep, q.H, q.W, k0.H, k0.W, q.C, coords.ptr,
+                                                      coords.ld, radius, scale, out.ptr, out.ld), "corr_direct_rep_fwd")
         return out
 
     # -- prior-motion stage: K14-K17 (csrc/prior.hip) -----------------------------------------------------------------

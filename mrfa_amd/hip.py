@@ -168,6 +168,7 @@ _SIGNATURES = {
     "mrfa_corr_lookup_fwd": ([_V, _V, _V, _I, _I, _V, _I, _L, _I, _V, _I], C.c_int),
     "mrfa_corr_lookup_bwd": ([_V, _V, _V, _I, _I, _V, _I, _L, _I, _V, _I, _V, _V, _V, _I], C.c_int),
     "mrfa_corr_direct_fwd": ([_V, _V, _I, _V, _I, _V, _I, _I, _I, _I, _I, _I, _I, _V, _I, _I, _F, _V, _I], C.c_int),
+    "mrfa_corr_direct_rep_fwd": ([_V, _V, _I, _V, _I, _V, _I, _I, _I, _I, _I, _I, _I, _I, _V, _I, _I, _F, _V, _I], C.c_int),
     "mrfa_nchw_to_nhwc": ([_V, _V, _V, _I, _I, _I, _I, _I, _I], C.c_int),
     "mrfa_nhwc_to_nchw": ([_V, _V, _I, _V, _I, _I, _I, _I, _I], C.c_int),
     "mrfa_avgpool2_fwd": ([_V, _V, _I, _I, _I, _I, _I, _V, _I], C.c_int),

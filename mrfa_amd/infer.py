@@ -9,6 +9,7 @@ from typing import Optional
 import torch
 from torch import nn
 
+from .modules.dense_motion import repeat_frames
 from .modules.raft import check_corr
 
 
@@ -18,18 +19,38 @@ def _check_cache_dtype(cache_dtype):
     return cache_dtype
 
 
+def _expand_kp(kp: dict, T: int) -> dict:
+    """the keypoint dict of Bs images for the Bs T frames of a clip group: element n of the result is element n // T"""
+    return kp if T == 1 else {k: (repeat_frames(v, T) if torch.is_tensor(v) else v) for k, v in kp.items()}
+
+
+def _frames_per_source(b: int, bs: int, what: str) -> int:
+    if b < bs or b % bs != 0:
+        raise ValueError(f"{what}: the driving batch {b} is no multiple of the source batch {bs} (every source needs the same number of frames, "
+                         "consecutive: frame n belongs to source n // T)")
+    return b // bs
+
+
 class Animator:
     def __init__(self, model: nn.Module, graph: bool = False, cache_dtype: torch.dtype = torch.float32, corr: str = "volume"):
         """model: mrfa_amd.train.HotPath or mrfa_amd.modules.model.MRFA (attributes encoder / dense_motion / decoder / down).
         cache_dtype: storage of the cached source feature pyramid (RaftFlow.encode_source(feature_dtype=)); torch.bfloat16 halves what the cache holds
         and what the per-frame warps gather, at the cost of one rounding of the source features.
-        corr: RaftFlow.forward(corr=): "direct" correlates each looked-up window where it is read and builds no correlation volume per frame"""
+        corr: RaftFlow.forward(corr=): "direct" correlates each looked-up window where it is read and builds no correlation volume per frame.
+        After set_source of Bs sources a call takes Bs T driving frames for any T >= 1, frame n driving source n // T: one batch-(Bs T) program against the
+        one cached copy of every source (the frames of a clip, T at a time).  graph=True keeps one captured program per T it has seen."""
         self.m = model.eval()
         self.use_graph = graph
         self.cache_dtype = _check_cache_dtype(cache_dtype)
         self.corr = check_corr(corr)
         self.source = None
-        self._g: Optional[torch.cuda.CUDAGraph] = None
+        self._graphs: dict = {}                               # T -> (graph, static driving frames, static output)
+        self._kp_s_rep: dict = {}                             # T -> source keypoints expanded to the Bs T frames
+
+    @property
+    def _g(self) -> Optional[torch.cuda.CUDAGraph]:
+        """the captured one-frame-per-source program (T == 1), if any"""
+        return self._graphs[1][0] if 1 in self._graphs else None
 
     @torch.no_grad()
     def set_source(self, source: torch.Tensor):
@@ -38,44 +59,51 @@ class Animator:
         self.kp_s = m.encoder(source)
         self.img_down = m.down(source)
         self.cache = m.decoder.encode_source(self.kp_s["kp"], self.img_down, source, feature_dtype=self.cache_dtype)
-        self._g = None
+        self._graphs, self._kp_s_rep = {}, {}
+
+    def _kp_source(self, T: int) -> dict:
+        if T not in self._kp_s_rep:                           # once per T, not per call
+            self._kp_s_rep[T] = _expand_kp(self.kp_s, T)
+        return self._kp_s_rep[T]
 
     @torch.no_grad()
     def _frame(self, driving):
         m = self.m
+        T = _frames_per_source(driving.shape[0], self.source.shape[0], "Animator")
         kp_d = m.encoder(driving)
-        dm = m.dense_motion(self.source, kp_d, self.kp_s)
+        dm = m.dense_motion(self.source, kp_d, self._kp_source(T))
         out, _, _ = m.decoder(self.kp_s["kp"], kp_d["kp"], dm, img=self.img_down, img_full=self.source, source_cache=self.cache, corr=self.corr)
         return out
 
     @torch.no_grad()
     def __call__(self, driving: torch.Tensor) -> torch.Tensor:
         assert self.source is not None, "call set_source(source) first"
+        T = _frames_per_source(driving.shape[0], self.source.shape[0], "Animator")
         if not self.use_graph:
             return self._frame(driving)
-        if self._g is None:                                   # capture the per-frame program once per source
+        if T not in self._graphs:                             # capture the program of T frames per source once per source and T
             from . import graph_replay_safe
             graph_replay_safe("Animator(graph=True)")
-            self._drv = driving.clone()
-            eager = self._frame(self._drv).clone()            # packs / tables outside the graph
+            drv = driving.clone()
+            eager = self._frame(drv).clone()                  # packs / tables outside the graph
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                self._out = self._frame(self._drv)
-            self._g = g
+                out = self._frame(drv)
             for k in range(3):                                # first AND later replays against the eager frame (mrfa_amd/graph.py)
                 g.replay()
                 torch.cuda.synchronize()
-                diff = (self._out - eager).abs()
+                diff = (out - eager).abs()
                 d, dm = float(diff.max()), float(diff.mean())
                 # run-to-run summation-order noise (split-K atomics) reaches ~1e-4 on single border pixels of sharply warped frames;
                 # a mis-ordered graph is wrong everywhere (stale or zero inputs): gate the mean tightly, the max loosely
                 if not (dm <= 2e-5 and d <= 5e-3):
-                    self._g = None
                     raise RuntimeError(f"Animator: hipGraph replay {k} differs from the eager frame (max |diff| {d:.3e}, mean {dm:.3e})")
-        self._drv.copy_(driving)
-        self._g.replay()
-        return self._out
+            self._graphs[T] = (g, drv, out)
+        g, drv, out = self._graphs[T]
+        drv.copy_(driving)
+        g.replay()
+        return out
 
 
 # ----------------------------------------------------------------------------------------------- callers of the path
@@ -124,41 +152,70 @@ def psnr(img1: torch.Tensor, img2: torch.Tensor):
     return 20 * torch.log10(1.0 / torch.sqrt(mse))
 
 
+def _check_frames_per_call(frames_per_call) -> int:
+    if not isinstance(frames_per_call, int) or frames_per_call < 1:
+        raise ValueError(f"frames_per_call must be an integer >= 1, not {frames_per_call!r}")
+    return frames_per_call
+
+
+def _clip_group(video: torch.Tensor, t0: int, T: int) -> torch.Tensor:
+    """frames t0 .. t0 + T - 1 of a clip (Bs,3,.,H,W) as a driving batch (Bs T,3,H,W): the frames of one source consecutive"""
+    g = video[:, :, t0:t0 + T]
+    return g.permute(0, 2, 1, 3, 4).reshape(g.shape[0] * g.shape[2], g.shape[1], g.shape[3], g.shape[4]).contiguous()
+
+
 @torch.no_grad()
-def reconstruction(model: nn.Module, video: torch.Tensor, graph: bool = False, cache_dtype: torch.dtype = torch.float32, corr: str = "volume"):
+def reconstruction(model: nn.Module, video: torch.Tensor, graph: bool = False, cache_dtype: torch.dtype = torch.float32, corr: str = "volume",
+                   frames_per_call: int = 1):
     """The reference's reconstruction loop (reconstruction.py:52-70) on one clip: source = frame 0, driving = every frame t,
     metrics mean|out - driving| and PSNR per frame.  video: (B,3,T,H,W) in [0,1].  The source is fixed for the whole clip, so
-    the source half of the path is computed once (Animator).  Returns {'prediction': (B,3,T,H,W), 'l1': [T], 'psnr': [T]}."""
+    the source half of the path is computed once (Animator).  frames_per_call: that many frames of the clip run as one batch against the one cached
+    source (a shorter last group at its own size).  Returns {'prediction': (B,3,T,H,W), 'l1': [T], 'psnr': [T]}."""
+    fpc = _check_frames_per_call(frames_per_call)
     anim = Animator(model, graph=graph, cache_dtype=cache_dtype, corr=corr)
     anim.set_source(video[:, :, 0].contiguous())
+    bs = video.shape[0]
     preds, l1, ps = [], [], []
-    for t in range(video.shape[2]):
-        driving = video[:, :, t].contiguous()
-        out = anim(driving).clone()
-        preds.append(out)
-        l1.append(float(torch.abs(out - driving).mean()))
-        ps.append(float(psnr(driving, out)))
+    for t0 in range(0, video.shape[2], fpc):
+        T = min(fpc, video.shape[2] - t0)
+        outs = anim(_clip_group(video, t0, T)).view(bs, T, *video.shape[1:2], *video.shape[3:])
+        for j in range(T):
+            driving = video[:, :, t0 + j].contiguous()
+            out = outs[:, j].clone()
+            preds.append(out)
+            l1.append(float(torch.abs(out - driving).mean()))
+            ps.append(float(psnr(driving, out)))
     return {"prediction": torch.stack(preds, dim=2), "l1": l1, "psnr": ps}
 
 
 @torch.no_grad()
 def make_animation(model: nn.Module, source: torch.Tensor, driving_video: torch.Tensor, relative: bool = True,
-                   adapt_movement_scale: bool = False, graph: bool = False, cache_dtype: torch.dtype = torch.float32, corr: str = "volume"):
+                   adapt_movement_scale: bool = False, graph: bool = False, cache_dtype: torch.dtype = torch.float32, corr: str = "volume",
+                   frames_per_call: int = 1):
     """demo.py:47-73 / animate_ddp.py:88-105: animate ONE source by the motion of a driving clip (B,3,T,H,W); with
-    relative=True the driving keypoints go through normalize_kp against the first driving frame.  Returns (B,3,T,H,W)."""
+    relative=True the driving keypoints go through normalize_kp against the first driving frame.  frames_per_call: that many frames of the clip run as
+    one batch against the one cached source (a shorter last group at its own size).  Returns (B,3,T,H,W)."""
     _check_cache_dtype(cache_dtype)
     check_corr(corr)
+    fpc = _check_frames_per_call(frames_per_call)
     m = model.eval()
     kp_s = m.encoder(source)
     img_down = m.down(source)
     cache = m.decoder.encode_source(kp_s["kp"], img_down, source, feature_dtype=cache_dtype)
     kp_init = m.encoder(driving_video[:, :, 0].contiguous())
+    bs, n = source.shape[0], driving_video.shape[2]
+    expanded = {}                                             # group size -> (kp_s, kp_init) expanded to it: at most the full and the tail size
     outs = []
-    for t in range(driving_video.shape[2]):
-        kp_d = m.encoder(driving_video[:, :, t].contiguous())
-        kp_n = normalize_kp(kp_s, kp_d, kp_init, adapt_movement_scale=adapt_movement_scale, use_relative_movement=relative,
+    for t0 in range(0, n, fpc):
+        T = min(fpc, n - t0)
+        if T not in expanded:
+            expanded[T] = (_expand_kp(kp_s, T), _expand_kp(kp_init, T))
+        kp_s_T, kp_init_T = expanded[T]
+        kp_d = m.encoder(_clip_group(driving_video, t0, T))
+        kp_n = normalize_kp(kp_s_T, kp_d, kp_init_T, adapt_movement_scale=adapt_movement_scale, use_relative_movement=relative,
                             use_relative_jacobian=relative)
-        dm = m.dense_motion(source, kp_n, kp_s)
+        dm = m.dense_motion(source, kp_n, kp_s_T)
         out, _, _ = m.decoder(kp_s["kp"], kp_n["kp"], dm, img=img_down, img_full=source, source_cache=cache, corr=corr)
-        outs.append(out.clone())
+        out = out.view(bs, T, *out.shape[1:])
+        outs.extend(out[:, j].clone() for j in range(T))
     return torch.stack(outs, dim=2)

@@ -5,8 +5,13 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from ..engine import Ctx, run_program
+from ..engine import Ctx, Storage, View, run_program
 from .util import AntiAliasInterpolation2d, Hourglass, kp2gaussian, make_coordinate_grid
+
+
+def repeat_frames(t: torch.Tensor, T: int) -> torch.Tensor:
+    """t.repeat_interleave(T, dim=0) as one strided copy (no repeat-count tensor: legal inside a hipGraph capture), contiguous; T == 1: t itself"""
+    return t if T == 1 else t.unsqueeze(1).expand(t.shape[0], T, *t.shape[1:]).reshape(t.shape[0] * T, *t.shape[1:]).contiguous()
 
 
 class DenseMotionNetwork(nn.Module):
@@ -30,6 +35,15 @@ class DenseMotionNetwork(nn.Module):
 
     def _program(self, e: Ctx, source_image, kd, ks, jd=None, js=None, bg=None):
         src = self.down.run(e, source_image) if self.scale_factor != 1 else e.from_nchw(source_image)   # (B,h,w,3)
+        T = kd.shape[0] // src.N
+        if T > 1:
+            # a clip (forward() checked the numbers): the anti-alias filter ran on the Bs sources; the prior-motion kernel reads source n for frame n, so
+            # the 1/4-scale image -- and it alone of the source -- is repeated for the T frames of its source (one copy of <= 3 h w floats per frame), the
+            # source keypoints / Jacobians likewise where the caller has not expanded them already
+            data = repeat_frames(src.st.data.view(src.N, src.H * src.W, src.ld), T)
+            src = View(Storage(data.reshape(-1, src.ld)), src.N * T, src.H, src.W, src.C, src.coff)
+            ks = repeat_frames(ks, kd.shape[0] // ks.shape[0])
+            js = repeat_frames(js, kd.shape[0] // js.shape[0]) if js is not None else None
         b, h, w, c = src.N, src.H, src.W, src.C
         k1 = self.num_kp + 1
         var = self.kp_variance
@@ -53,6 +67,16 @@ class DenseMotionNetwork(nn.Module):
     def forward(self, source_image, kp_driving, kp_source, bg_param=None, dropout_flag=False, dropout_p=0):
         if dropout_flag:
             raise NotImplementedError("dropout_softmax belongs to the TPSM prior (out of scope)")
+        bs, b = source_image.shape[0], kp_driving['kp'].shape[0]
+        if b != bs or kp_source['kp'].shape[0] != bs:
+            # a clip: B = Bs T driving frames, frame n of source n // T; kp_source at the source batch or already expanded to B
+            if b % bs != 0:
+                raise ValueError(f"DenseMotionNetwork: the driving batch {b} is no multiple of the source batch {bs} (every source needs the same number of frames, consecutive)")
+            if kp_source['kp'].shape[0] not in (bs, b):
+                raise ValueError(f"DenseMotionNetwork: kp_source holds {kp_source['kp'].shape[0]} images, neither the {bs} sources nor the {b} driving frames")
+            ins_grad = [source_image] + [v for d in (kp_driving, kp_source) for v in d.values() if torch.is_tensor(v)]
+            if self.training or (torch.is_grad_enabled() and any(t.requires_grad for t in (*self.parameters(), *ins_grad))):
+                raise ValueError(f"DenseMotionNetwork: {b} driving frames for {bs} sources is an inference mode (a shared source has no backward): eval() and torch.no_grad()")
         ins = [source_image, kp_driving['kp'], kp_source['kp']]
         has_jac = 'jacobian' in kp_driving
         if has_jac:

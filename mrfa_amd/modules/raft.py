@@ -137,10 +137,17 @@ class _CorrVolume:
         self.e, self.q, self.k, self.kp, self.scale = e, q, k, kpool, scale
         B, Q, S0, S1, D = q.N, q.H * q.W, k.H * k.W, kpool.H * kpool.W, q.C
         self.B, self.Q, self.S0, self.S1, self.D = B, Q, S0, S1, D
+        # a clip: the T = q.N / k.N frames of one source are consecutive, so their T Q query rows are ONE GEMM operand against that source's keys --
+        # k.N problems of T Q rows, the volumes in the same (B Q, S) row order (T == 1: the launch of one problem per image)
+        Bs = k.N
+        T = B // Bs
+        assert Bs * T == B and kpool.N == Bs, "_CorrVolume: the frames of every source, consecutive"
+        if T > 1 and e.record:
+            raise RuntimeError("_CorrVolume: a key image shared by several query images has no backward, not legal in a recording (training) program")
         self.vol0 = torch.empty((B * Q, S0), dtype=torch.float32, device=e.dev)
         self.vol1 = torch.empty((B * Q, S1), dtype=torch.float32, device=e.dev)
-        e.gemm_nt(q.ptr, q.ld, k.ptr, k.ld, self.vol0.data_ptr(), S0, Q, S0, D, scale, B, Q * q.ld, S0 * k.ld, Q * S0)
-        e.gemm_nt(q.ptr, q.ld, kpool.ptr, kpool.ld, self.vol1.data_ptr(), S1, Q, S1, D, scale, B, Q * q.ld, S1 * kpool.ld, Q * S1)
+        e.gemm_nt(q.ptr, q.ld, k.ptr, k.ld, self.vol0.data_ptr(), S0, T * Q, S0, D, scale, Bs, T * Q * q.ld, S0 * k.ld, T * Q * S0)
+        e.gemm_nt(q.ptr, q.ld, kpool.ptr, kpool.ld, self.vol1.data_ptr(), S1, T * Q, S1, D, scale, Bs, T * Q * q.ld, S1 * kpool.ld, T * Q * S1)
         self.dvol0 = self.dvol1 = None
         if e.record:
             e.tape.append(self._bwd)
@@ -262,13 +269,17 @@ class RaftFlow(nn.Module):
 
     def _program(self, e: Ctx, kp_s, kp_d, deformation, occlusion, img, img_full, cache=None, corr="volume"):
         gen = self.generator
+        # b: the DRIVING batch.  With a source cache it may be T times the source batch (a clip: frame n belongs to source n // T, forward() checked
+        # the numbers); the source side -- imgf, the pyramid, k_s / pooled k_s -- stays at the source batch and every reader of it divides by T
+        b, h, w = deformation.shape[0], img.shape[2], img.shape[3]
         if cache is not None:
-            assert not e.record and cache["shape"] == tuple(img_full.shape), "source cache: inference only, same source batch"
+            assert not e.record and b % cache["shape"][0] == 0, "source cache: inference only, whole clips of every source"
             imgf, feature = cache["imgf"], cache["feature"]
         else:
             imgf = e.from_nchw(img_full)
             feature = gen.run_encode(e, imgf)
-        b, h, w = img.shape[0], img.shape[2], img.shape[3]
+        T = b // imgf.N
+        assert imgf.N * T == b
         size = self.size
         deform = e.wrap_nhwc(deformation.contiguous())                          # (B,h,w,2) normalised sampling grid
         prior_occ = e.wrap_nhwc(occlusion.contiguous().view(b, h, w, 1))        # logits
@@ -285,9 +296,9 @@ class RaftFlow(nn.Module):
                     occ_res = e.resize(prior_occ, f.H, f.W)
                 else:
                     grid_res, occ_res = deform, prior_occ
-                warp_f.append(e.grid_sample(f, grid_res, 0))
+                warp_f.append(e.grid_sample(f, grid_res, 0, in_rep=T))
                 occs.append(e.act(occ_res, 2))
-            warp_img = e.grid_sample(imgf, grid_res, 0, need_din=False)
+            warp_img = e.grid_sample(imgf, grid_res, 0, in_rep=T, need_din=False)
             out = gen.run_decode(e, warp_f, warp_img, occs, None)
             outs = (e.to_nchw(out), e.to_nchw(warp_img), self._strip(e, occs))
             seed = ((lambda g: e.seed_grad_nchw(out, g)), (lambda g: e.seed_grad_nchw(warp_img, g)), None)
@@ -348,12 +359,12 @@ class RaftFlow(nn.Module):
             if vols is not None:
                 cfeat = e.corr_lookup(vols[lv].vol0, vols[lv].vol1, vols[lv].dvols, h, w, coords)
             else:
-                cfeat = e.corr_direct(q_levels[lv], k_s, k_pool, coords, self.scale)
+                cfeat = e.corr_direct(q_levels[lv], k_s, k_pool, coords, self.scale, k_rep=T)
             if i > base:
                 cfeat = e.resize(cfeat, r, r)
             inp = e.new(b, r, r, 256)
             self.corr_enc.run(e, flow, cfeat, inp)
-            ctx = e.grid_sample(f, flow, 1)
+            ctx = e.grid_sample(f, flow, 1, in_rep=T)
             ctx = e.conv(ctx, self.to_context[i], relu=True)
             d_flow = self.refine.run(e, inp, ctx, ctx_relu=True)
             # the running-flow / occlusion updates (raft.py:258-262), the coarse grid of this level and the re-composition for the next one (raft.py:276-295):
@@ -384,15 +395,15 @@ class RaftFlow(nn.Module):
                         no = e.resize(d_flow.slice(2, 3), r2, r2)
                         e.resize(d_occ_pre, r2, r2, out=no, acc=True)
                         d_f_pre, d_occ_pre = nd, no
-            out_warp_f.append(e.grid_sample(f, flow_w, 1))
+            out_warp_f.append(e.grid_sample(f, flow_w, 1, in_rep=T))
             out_occ.append(e.act(occ_new, 2))
             # coarse (prior-motion) warp straight into its decode concat slot (raft.py:265-272); level 5's is never read
             if i < gen.num_up_blocks:
-                e.grid_sample(f, grid_c, 0, out=cats[i].slice(lv_c[i], 2 * lv_c[i]))
+                e.grid_sample(f, grid_c, 0, out=cats[i].slice(lv_c[i], 2 * lv_c[i]), in_rep=T)
             if i < self.num_iter - 1:
                 flow, occ = nflow, nocc
         # NB: the image is warped with the last level's INPUT flow, not flow_w (raft.py:302)
-        warp_img = e.grid_sample(imgf, flow, 1, need_din=False)
+        warp_img = e.grid_sample(imgf, flow, 1, in_rep=T, need_din=False)
         out = gen.run_decode(e, out_warp_f, warp_img, out_occ, cats)
         strip = self._strip(e, out_occ + [e.act(prior_occ, 2)])
         outs = (e.to_nchw(out), e.to_nchw(warp_img), strip)
@@ -403,13 +414,27 @@ class RaftFlow(nn.Module):
         """source_cache (extension, inference only): the result of encode_source(kp_s, img, img_full) for this source.
         corr (extension): "volume" builds the all-pairs correlation volumes of every query level and looks the windows up in them (the reference's program);
         "direct" (inference only: it has no backward) computes each looked-up window from the queries and keys instead and builds no volume -- the same
-        values up to fp32 summation order, none of the volumes' memory."""
+        values up to fp32 summation order, none of the volumes' memory.
+        A clip (extension, inference only): with a source_cache of Bs sources, kp_d and dense_motion may hold B = Bs T driving frames, frame n belonging to
+        source n // T (the frames of one source consecutive); kp_s, img and img_full stay at Bs and nothing of the source is replicated."""
         if check_corr(corr) == "direct":
             if self.training:
                 raise ValueError('corr="direct" is an inference mode (the direct correlation kernel has no backward): call eval() first, training keeps the volumes')
             ins_grad = (kp_s, kp_d, dense_motion['deformation'], dense_motion['occlusion'])
             if torch.is_grad_enabled() and any(t.requires_grad for t in (*self.parameters(), *ins_grad)):
                 raise ValueError('corr="direct" has no backward: run it under torch.no_grad() (gradients are enabled and a parameter or input requires one)')
+        bs = source_cache["shape"][0] if source_cache is not None else img_full.shape[0]
+        b = dense_motion['deformation'].shape[0]
+        if b != bs:
+            if source_cache is None:
+                raise ValueError(f"RaftFlow.forward: {b} driving frames for {bs} sources needs a source_cache (encode_source): only a cached source is shared by the frames of a clip")
+            if self.training:
+                raise ValueError(f"RaftFlow.forward: {b} driving frames for {bs} sources is an inference mode (a shared source has no backward): call eval() first")
+            ins_grad = (kp_s, kp_d, dense_motion['deformation'], dense_motion['occlusion'])
+            if torch.is_grad_enabled() and any(t.requires_grad for t in (*self.parameters(), *ins_grad)):
+                raise ValueError(f"RaftFlow.forward: {b} driving frames for {bs} sources has no backward: run it under torch.no_grad() (gradients are enabled and a parameter or input requires one)")
+            if b % bs != 0:
+                raise ValueError(f"RaftFlow.forward: the driving batch {b} is no multiple of the source batch {bs} (every source needs the same number of frames, consecutive)")
         if img is None:
             raise ValueError("RaftFlow.forward needs `img` (the 1/4-resolution source); the reference crashes on None too "
                              "(raft.py:144-145 uses a commented-out self.down)")

@@ -6,6 +6,9 @@
                                                                     # alternating rounds of both modes in ONE process: median and spread per mode
     python tools/bench_animator.py --corr volume direct --raft-forward --size 512 --batch 4
                                                                     # the RaftFlow forward of bench.py's 512^2 inference configuration, graphed
+    python tools/bench_animator.py --frames 1 2 4 8 --corr volume direct --rounds 7
+                                                                    # a clip of ONE source, T frames per call: the clip Animator (one cached source), the
+                                                                    # replicated-source batch-T Animator and the per-frame Animator, alternating round by round
 """
 import argparse
 import copy
@@ -29,6 +32,9 @@ ap.add_argument("--batch", type=int, nargs="+", default=[1, 8])
 ap.add_argument("--rounds", type=int, default=1, help="timed rounds per mode (20 frames each); > 1 prints median and min-max")
 ap.add_argument("--raft-forward", action="store_true", help="time the graphed RaftFlow forward on fixed prior inputs instead of the Animator frame")
 ap.add_argument("--no-graph", action="store_true")
+ap.add_argument("--frames", type=int, nargs="+", default=None, metavar="T",
+                help="frames of one source per call: times Animator calls of T frames against one cached source, against the source replicated T times, and "
+                     "per frame (replaces the --batch report)")
 a = ap.parse_args()
 
 dev = torch.device("cuda", 0)
@@ -107,6 +113,59 @@ def animator_steps(B):
         steps[corr] = lambda an=an: an(drv)
     return steps
 
+
+def build_model():
+    model = HotPath(cfg)
+    for pfx, mod in (("encoder.", model.encoder), ("dense_motion.", model.dense_motion), ("decoder.", model.decoder)):
+        mod.load_state_dict(fill_state_dict(mod.state_dict(), tag=pfx))
+    return model.to(dev).eval()
+
+
+def clip_report():
+    """one source, T driving frames per call; per corr mode and T three Animators in one process: "clip" (set_source of the ONE source, calls of T frames),
+    "replicated" (set_source of the source repeated T times: the same batch-T program on T copies) and "per-frame" (T = 1, the path without this option)"""
+    model = build_model()
+    src = det_uniform("ba/src", (1, 3, a.size, a.size), 0, 1).to(dev)
+    drv = det_uniform("ba/clip", (max(a.frames), 3, a.size, a.size), 0, 1).to(dev)
+
+    def make(source, frames, corr):
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        an = Animator(model, graph=not a.no_graph, corr=corr)
+        an.set_source(source)
+        an(frames)                                            # (graph=True: the capture; its pool stays allocated)
+        torch.cuda.synchronize()
+        return (lambda: an(frames)), (torch.cuda.memory_allocated() - base) / 1e6
+    for corr in a.corr:
+        for T in a.frames:
+            frames = drv[:T].contiguous()
+            steps, mem = {}, {}
+            steps["per-frame"], mem["per-frame"] = make(src, frames[:1].contiguous(), corr)
+            steps["clip"], mem["clip"] = make(src, frames, corr)
+            steps["replicated"], mem["replicated"] = make(src.repeat_interleave(T, dim=0).contiguous(), frames, corr)
+            d = (steps["clip"]().clone() - steps["replicated"]()).abs()
+            times = {k: [] for k in steps}
+            for fn in steps.values():
+                for _ in range(3):
+                    fn()
+            for _ in range(a.rounds):
+                for k, fn in steps.items():                   # the three alternate round by round: same box, same minute
+                    times[k].append(timed(fn))
+            print(f"{a.size}^2 corr={corr} T={T}: clip vs replicated output max |diff| {d.max().item():.3e} mean {d.mean().item():.3e}")
+            for k, ts in times.items():
+                n = 1 if k == "per-frame" else T
+                per = [t / n for t in ts]
+                print(f"{a.size}^2 corr={corr} T={T}: {k:10s} per call {summary(ts)}; per frame {statistics.median(per):.3f} ms ({min(per):.3f} - {max(per):.3f}), "
+                      f"{1e3 / statistics.median(per):.0f} frames/s; device memory held {mem[k]:.1f} MB")
+            del steps
+
+
+if a.frames:
+    if min(a.frames) < 1:
+        ap.error("--frames: T >= 1")
+    with torch.no_grad():
+        clip_report()
+    sys.exit(0)
 
 for B in a.batch:
     with torch.no_grad():
