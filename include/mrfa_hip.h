@@ -49,7 +49,9 @@ const char* mrfa_last_error(void);
  *  11  mrfa_corr_direct_fwd(): the correlation window computed from queries and keys where it is read, without the volumes (no struct changed: a version-10
  *      client still works against this library, not the reverse).
  *      Still 11: mrfa_corr_direct_rep_fwd() (k_rep consecutive query images read one key image: a clip of one source) is additive -- no struct and no existing
- *      entry changed, so the number stays; a client that wants it looks the symbol up and treats its absence as an older version-11 library.             */
+ *      entry changed, so the number stays; a client that wants it looks the symbol up and treats its absence as an older version-11 library.
+ *      Still 11: mrfa_kp_relative_fwd() (the relative keypoints of an animation loop, first driving frame and source indexed per clip) is additive in the
+ *      same way; the number stays and a client looks the symbol up.                                                                                      */
 #define MRFA_ABI_VERSION 11
 int mrfa_version(void);
 
@@ -554,6 +556,18 @@ typedef struct mrfa_prior_params {
 } mrfa_prior_params;
 int mrfa_prior_motion_fwd(void* stream, const mrfa_prior_params* p);
 int mrfa_prior_motion_bwd(void* stream, const mrfa_prior_params* p);
+
+/* Relative-motion transfer of an animation loop (reference animate_ddp.py:17-37, normalize_kp with use_relative_movement) for B driving frames, `rep`
+ * consecutive frames per source: frame n reads the first driving frame and the source at m = n / rep (kp_0, jac_0, kp_s, jac_s hold B / rep entries).
+ *   kp_out[n,k]  = (kp_d[n,k] - kp_0[m,k]) * scale + kp_s[m,k]          (difference, times scale, plus source: the reference's order)
+ *   jac_out[n,k] = jac_d[n,k] inv(jac_0[m,k]) jac_s[m,k]                (closed-form 2x2 inverse; computed as ((J_d adj J_0) J_s) / det J_0)
+ * scale points to ONE float in device memory (read by the kernel: no host round trip, and a captured graph follows a new value), or is null for 1.
+ * The four Jacobian pointers are all null (keypoints only) or all given.  Refused with a message (outputs untouched): a partial Jacobian set; a null
+ * kp_d / kp_0 / kp_s / kp_out; B, K or rep < 1; B % rep != 0; a keypoint pointer that is not 8-byte or a Jacobian pointer that is not 16-byte aligned.
+ * The outputs must not alias any input (the kernel reads entry m of kp_0 / kp_s from rep threads); inputs are never written.  A singular jac_0 gives
+ * non-finite Jacobians where torch.inverse would raise.  One thread per (n, k), no LDS and no atomics: two runs are bit-identical.  No backward.          */
+int mrfa_kp_relative_fwd(void* stream, const float* kp_d, const float* jac_d, const float* kp_0, const float* jac_0, const float* kp_s,
+                         const float* jac_s, const float* scale, int B, int rep, int K, float* kp_out, float* jac_out);
 
 /* K14+K17: mask = softmax over the K1 = K+1 motions of logit (B,H,W,K1 NHWC, ldl); deformation (B,H,W,2) = sum_k mask_k motion_k
  * (reference modules/dense_motion.py:129-136); also exports mask and the logits as NCHW (B,K1,H,W) (the returned `mask`,

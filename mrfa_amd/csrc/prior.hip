@@ -7,6 +7,7 @@
 //   prior_motion     dense_motion.py:36-46 (heat-map differences), 48-76 (sparse motions, closed-form 2x2 inverse, background
 //                    affine), 78-85 (the K+1 warps of the 1/4-scale source, grid_sample align_corners=False) and the channel
 //                    interleave of :118 -> hourglass input, motions, sparse_deformed
+//   kp_relative      animate_ddp.py:17-37 (normalize_kp: relative keypoints and Jacobians of a clip's frames), inference only
 //   softmax_combine  dense_motion.py:129-136 (softmax over the K+1 motions, mask-weighted deformation)
 //   kp_head          kp_detector.py:90-120 (spatial softmax at temperature T, soft-argmax, heat-map-weighted Jacobian pooling)
 //
@@ -262,6 +263,33 @@ __global__ __launch_bounds__(NT) void prior_motion_bwd_kernel(const mrfa_prior_p
     }
 }
 
+// ------------------------------------------------------------------------------------------------ kp_relative
+// one thread per (n, k): the relative-motion transfer of an animation loop (normalize_kp, animate_ddp.py:17-37) with the first driving frame and the
+// source indexed at m = n / rep, so a clip of rep frames per source needs no repeated copies of either.  No LDS, no atomics: bit-identical run to run.
+// Rounding order (tests/test_relative_gpu.py counts it): kp = ((kd - k0) * s) + ks;  jac = ((Jd adj(J0)) Js) / (a d - b c), J0 = [a b; c d].
+__global__ __launch_bounds__(NT) void kp_relative_fwd_kernel(const float2* __restrict__ kd, const float4* __restrict__ jd, const float2* __restrict__ k0,
+                                                             const float4* __restrict__ j0, const float2* __restrict__ ks,
+                                                             const float4* __restrict__ js, const float* __restrict__ scale, int B, int rep, int K,
+                                                             float2* __restrict__ kp_out, float4* __restrict__ jac_out) {
+    const long long total = (long long)B * K;
+    const float s = scale ? scale[0] : 1.f;
+    for (long long i = blockIdx.x * (long long)NT + threadIdx.x; i < total; i += (long long)gridDim.x * NT) {
+        const int k = (int)(i % K), n = (int)(i / K);
+        const size_t o = (size_t)(n / rep) * K + k;
+        const float2 d = kd[i], z = k0[o], c = ks[o];
+        kp_out[i] = make_float2((d.x - z.x) * s + c.x, (d.y - z.y) * s + c.y);
+        if (jd) {
+            const float4 D = jd[i], Z = j0[o], S = js[o];                    // row-major 2x2: (x y; z w)
+            const float det = Z.x * Z.w - Z.y * Z.z;
+            // P = D adj(Z), adj(Z) = (w -y; -z x)
+            const float p00 = D.x * Z.w - D.y * Z.z, p01 = D.y * Z.x - D.x * Z.y;
+            const float p10 = D.z * Z.w - D.w * Z.z, p11 = D.w * Z.x - D.z * Z.y;
+            jac_out[i] = make_float4((p00 * S.x + p01 * S.z) / det, (p00 * S.y + p01 * S.w) / det,
+                                     (p10 * S.x + p11 * S.z) / det, (p10 * S.y + p11 * S.w) / det);
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ softmax_combine
 constexpr int MAXK1 = 32;
 
@@ -426,6 +454,25 @@ extern "C" int mrfa_prior_motion_bwd(void* stream, const mrfa_prior_params* pp) 
     MRFA_CHECK_ARG(p.dinp && p.lddi >= (p.K + 1) * (p.C + 1), "prior_motion_bwd: gradient of the hourglass input buffer");
     hipLaunchKernelGGL(prior_motion_bwd_kernel, dim3(p.B * (p.K + 1)), dim3(NT), 0, (hipStream_t)stream, p);
     MRFA_CHECK_LAUNCH("mrfa_prior_motion_bwd");
+    return 0;
+}
+
+extern "C" int mrfa_kp_relative_fwd(void* stream, const float* kp_d, const float* jac_d, const float* kp_0, const float* jac_0, const float* kp_s,
+                                    const float* jac_s, const float* scale, int B, int rep, int K, float* kp_out, float* jac_out) {
+    MRFA_CHECK_ARG(kp_d && kp_0 && kp_s && kp_out, "kp_relative_fwd: null keypoint pointer");
+    MRFA_CHECK_ARG(B >= 1 && K >= 1 && rep >= 1, "kp_relative_fwd: B, K and rep must be >= 1 (B %d, K %d, rep %d)", B, K, rep);
+    MRFA_CHECK_ARG(B % rep == 0, "kp_relative_fwd: rep must divide B (B %d, rep %d)", B, rep);
+    const int njac = (jac_d != nullptr) + (jac_0 != nullptr) + (jac_s != nullptr) + (jac_out != nullptr);
+    MRFA_CHECK_ARG(njac == 0 || njac == 4, "kp_relative_fwd: the four Jacobian pointers come together or not at all (%d of 4 given)", njac);
+    const uintptr_t a8 = (uintptr_t)kp_d | (uintptr_t)kp_0 | (uintptr_t)kp_s | (uintptr_t)kp_out;
+    const uintptr_t a16 = (uintptr_t)jac_d | (uintptr_t)jac_0 | (uintptr_t)jac_s | (uintptr_t)jac_out;
+    MRFA_CHECK_ARG((a8 & 7u) == 0 && (a16 & 15u) == 0 && (scale == nullptr || ((uintptr_t)scale & 3u) == 0),
+                   "kp_relative_fwd: keypoints must be 8-byte aligned and Jacobians 16-byte aligned (vector loads and stores)");
+    const long long total = (long long)B * K;
+    hipLaunchKernelGGL(kp_relative_fwd_kernel, dim3(stream_grid(total, NT)), dim3(NT), 0, (hipStream_t)stream, (const float2*)kp_d, (const float4*)jac_d,
+                       (const float2*)kp_0, (const float4*)jac_0, (const float2*)kp_s, (const float4*)jac_s, scale, B, rep, K, (float2*)kp_out,
+                       (float4*)jac_out);
+    MRFA_CHECK_LAUNCH("mrfa_kp_relative_fwd");
     return 0;
 }
 

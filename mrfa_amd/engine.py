@@ -1803,6 +1803,55 @@ class Ctx:
             self.tape.append(bwd)
         return out
 
+    def kp_relative(self, kd, k0, ks, jd=None, j0=None, js=None, scale: Optional[torch.Tensor] = None, rep: int = 1):
+        """(kd - k0) * scale + ks and jd inv(j0) js of normalize_kp (animate_ddp.py:17-37) in one launch: kd / jd (B,K,2) / (B,K,2,2) of the driving frames,
+        k0 / j0 and ks / js of the B / rep first driving frames and sources (frame n reads entry n // rep).  scale: a one-element fp32 DEVICE tensor (the
+        kernel reads it) or None for 1.  -> (kp, jacobian or None), fresh tensors.  The kernel loads float2 / float4: an operand that is a view at an
+        offset which is not 8-byte (keypoints) / 16-byte (Jacobians) aligned is copied first.  Inference only: the kernel has no backward.
+        A version-11 library built before mrfa_kp_relative_fwd existed (the entry is additive: hip.ADDITIVE_SYMBOLS) has no such kernel; then, with ONE
+        RuntimeWarning per process, the same arithmetic runs as torch operations (normalize_kp's launches, on expanded views of k0 / ks)."""
+        if self.record:
+            raise RuntimeError("Ctx.kp_relative: the relative keypoints have no backward, not legal in a recording (training) program")
+        jacs = (jd, j0, js)
+        assert all(j is None for j in jacs) or all(j is not None for j in jacs), "kp_relative: the three Jacobians come together or not at all"
+        kd, k0, ks = (self._aligned(self._cf(t), 8) for t in (kd, k0, ks))
+        jd, j0, js = (self._aligned(self._cf(t), 16) for t in jacs)
+        B, K = kd.shape[0], kd.shape[1]
+        assert rep >= 1 and B == k0.shape[0] * rep == ks.shape[0] * rep and k0.shape[1] == ks.shape[1] == K, \
+            f"kp_relative: entry n // rep for frame n ({B} frames, {k0.shape[0]} initial frames, {ks.shape[0]} sources, rep {rep})"
+        if scale is not None:
+            assert scale.dtype == torch.float32 and scale.numel() == 1 and scale.device == kd.device, "kp_relative: scale is one fp32 element on the keypoints' device"
+        if not hip.has("mrfa_kp_relative_fwd"):
+            return self._kp_relative_older_library(kd, k0, ks, jd, j0, js, scale, rep)
+        kp_out = torch.empty_like(kd)
+        jac_out = torch.empty_like(jd) if jd is not None else None
+        p = lambda t: None if t is None else t.data_ptr()
+        self._chk(self.L.mrfa_kp_relative_fwd(self.s, p(kd), p(jd), p(k0), p(j0), p(ks), p(js), p(scale), B, rep, K, p(kp_out), p(jac_out)), "kp_relative_fwd")
+        return kp_out, jac_out
+
+    @staticmethod
+    def _aligned(t: Optional[torch.Tensor], nbytes: int) -> Optional[torch.Tensor]:
+        return t if t is None or t.data_ptr() % nbytes == 0 else t.clone()
+
+    _warned_no_kp_relative = False
+
+    @staticmethod
+    def _kp_relative_older_library(kd, k0, ks, jd, j0, js, scale, rep):
+        if not Ctx._warned_no_kp_relative:
+            Ctx._warned_no_kp_relative = True
+            import warnings
+            warnings.warn(f"the loaded version-{hip.ABI_VERSION} library has no mrfa_kp_relative_fwd (it was built before the entry was added): the relative "
+                          "keypoints run as torch operations, about twenty small launches per call.  Rebuild it with `python -m mrfa_amd.build --force`",
+                          RuntimeWarning, stacklevel=3)
+        rf = lambda t: t if rep == 1 else t.unsqueeze(1).expand(t.shape[0], rep, *t.shape[1:]).reshape(t.shape[0] * rep, *t.shape[1:])
+        kp = (kd - rf(k0)) * (scale if scale is not None else 1) + rf(ks)
+        if jd is None:
+            return kp, None
+        z = rf(j0)
+        a, b, c, d = z[..., 0, 0], z[..., 0, 1], z[..., 1, 0], z[..., 1, 1]
+        inv = torch.stack([torch.stack([d, -b], dim=-1), torch.stack([-c, a], dim=-1)], dim=-2) / (a * d - b * c)[..., None, None]
+        return kp, torch.matmul(torch.matmul(jd, inv), rf(js))
+
     def prior_motion(self, src: View, kd, ks, jd, js, bg, variance: float):
         """DenseMotionNetwork's heat-map differences, sparse motions and the K+1 warps of the 1/4-scale source in one launch
         (dense_motion.py:36-85, 117-119) -> (motions View (B*K1,h,w,2), hourglass input View (B,h,w,K1*(C+1)), sparse_deformed IslandOut)"""

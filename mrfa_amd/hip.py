@@ -211,6 +211,7 @@ _SIGNATURES = {
     "mrfa_kp_gaussian_bwd": ([_V, _V, _I, _I, _I, _I, _F, _V, _I, _V, _V], C.c_int),
     "mrfa_prior_motion_fwd": ([_V, C.POINTER(PriorParams)], C.c_int),
     "mrfa_prior_motion_bwd": ([_V, C.POINTER(PriorParams)], C.c_int),
+    "mrfa_kp_relative_fwd": ([_V, _V, _V, _V, _V, _V, _V, _V, _I, _I, _I, _V, _V], C.c_int),
     "mrfa_softmax_combine_fwd": ([_V, _V, _I, _V, _I, _I, _I, _I, _I, _V, _V, _V], C.c_int),
     "mrfa_softmax_combine_bwd": ([_V, _V, _I, _I, _I, _I, _I, _V, _V, _V, _V, _V, _I, _V], C.c_int),
     "mrfa_kp_head_fwd": ([_V, _V, _I, _V, _I, _I, _I, _I, _I, _F, _V, _V, _V], C.c_int),
@@ -221,6 +222,9 @@ _SIGNATURES = {
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+# entries added to ABI version 11 without moving the number (include/mrfa_hip.h): a version-11 library built before one of them lacks it.  lib() loads such a
+# library; the one caller of the entry (engine.Ctx.kp_relative) looks the symbol up with has() and says what it does without it
+ADDITIVE_SYMBOLS = ("mrfa_kp_relative_fwd",)
 LN_SLOTS = 16          # MRFA_LN_SLOTS
 RESIZE_SUM_TERMS = 4   # MRFA_RESIZE_SUM_TERMS
 ABI_VERSION = 11       # MRFA_ABI_VERSION of include/mrfa_hip.h: the struct layouts above mirror THAT header; lib() refuses any other library
@@ -249,7 +253,9 @@ def lib():
                 "mrfa_amd has no CPU fallback.")
         L = C.CDLL(LIB_PATH)
         for name, (argtypes, restype) in _SIGNATURES.items():
-            fn = getattr(L, name)          # AttributeError if the ABI and the header drift apart
+            fn = getattr(L, name, None) if name in ADDITIVE_SYMBOLS else getattr(L, name)          # AttributeError if the ABI and the header drift apart
+            if fn is None:
+                continue
             fn.argtypes = argtypes
             fn.restype = restype
         if L.mrfa_version() != ABI_VERSION:
@@ -282,6 +288,11 @@ def set_mfma_mode(mode: str):
 def mfma_mode() -> str:
     m = lib().mrfa_get_mfma_mode()
     return next(k for k, v in MFMA_MODES.items() if v == m)
+
+
+def has(name: str) -> bool:
+    """whether the loaded library exports `name` (one of ADDITIVE_SYMBOLS; every other entry is there or lib() raised)"""
+    return getattr(lib(), name, None) is not None
 
 
 def check(rc: int, what: str):

@@ -32,20 +32,32 @@ def _frames_per_source(b: int, bs: int, what: str) -> int:
 
 
 class Animator:
-    def __init__(self, model: nn.Module, graph: bool = False, cache_dtype: torch.dtype = torch.float32, corr: str = "volume"):
+    def __init__(self, model: nn.Module, graph: bool = False, cache_dtype: torch.dtype = torch.float32, corr: str = "volume", relative: bool = False,
+                 adapt_movement_scale: bool = False, use_relative_jacobian: Optional[bool] = None):
         """model: mrfa_amd.train.HotPath or mrfa_amd.modules.model.MRFA (attributes encoder / dense_motion / decoder / down).
         cache_dtype: storage of the cached source feature pyramid (RaftFlow.encode_source(feature_dtype=)); torch.bfloat16 halves what the cache holds
         and what the per-frame warps gather, at the cost of one rounding of the source features.
         corr: RaftFlow.forward(corr=): "direct" correlates each looked-up window where it is read and builds no correlation volume per frame.
+        relative: the driving keypoints go through normalize_kp against an initial driving frame (set_source(source, driving_initial) or
+        set_driving_initial(frame), one frame per source) before the motion network sees them, as one kernel of the frame program (relative_kp);
+        adapt_movement_scale: the displacement is scaled by sqrt(hull area(source kp)) / sqrt(hull area(initial kp)) of batch element 0, kept on the device;
+        use_relative_jacobian: None follows `relative`.  relative=False ignores the other two, like normalize_kp, and is the absolute Animator call for call.
         After set_source of Bs sources a call takes Bs T driving frames for any T >= 1, frame n driving source n // T: one batch-(Bs T) program against the
         one cached copy of every source (the frames of a clip, T at a time).  graph=True keeps one captured program per T it has seen."""
         self.m = model.eval()
         self.use_graph = graph
         self.cache_dtype = _check_cache_dtype(cache_dtype)
         self.corr = check_corr(corr)
+        self.relative = bool(relative)
+        self.adapt_movement_scale = self.relative and bool(adapt_movement_scale)
+        self.relative_jacobian = self.relative and bool(relative if use_relative_jacobian is None else use_relative_jacobian)
         self.source = None
         self._graphs: dict = {}                               # T -> (graph, static driving frames, static output)
         self._kp_s_rep: dict = {}                             # T -> source keypoints expanded to the Bs T frames
+        # relative mode: keypoints of the initial driving frames (Bs of them) and the movement scale (one float on the device); a new initial frame or a
+        # new source drops the captured programs, which have the old tensors' addresses in them
+        self._kp_init: Optional[dict] = None
+        self._scale: Optional[torch.Tensor] = None
 
     @property
     def _g(self) -> Optional[torch.cuda.CUDAGraph]:
@@ -53,13 +65,35 @@ class Animator:
         return self._graphs[1][0] if 1 in self._graphs else None
 
     @torch.no_grad()
-    def set_source(self, source: torch.Tensor):
+    def set_source(self, source: torch.Tensor, driving_initial: Optional[torch.Tensor] = None):
+        """driving_initial (relative mode): set_driving_initial(driving_initial) after the source.  A new source drops the captured programs AND an initial
+        frame set earlier (the movement scale depends on both): pass it here or call set_driving_initial again."""
         m = self.m
         self.source = source
         self.kp_s = m.encoder(source)
         self.img_down = m.down(source)
         self.cache = m.decoder.encode_source(self.kp_s["kp"], self.img_down, source, feature_dtype=self.cache_dtype)
         self._graphs, self._kp_s_rep = {}, {}
+        self._kp_init = self._scale = None
+        if driving_initial is not None:
+            self.set_driving_initial(driving_initial)
+
+    @torch.no_grad()
+    def set_driving_initial(self, frame: torch.Tensor):
+        """frame (Bs,3,H,W): the driving frame whose keypoints the relative motion is measured from, one per source (the first frame of the driving clip in
+        demo.py:47-73; demo.py:150-157's best frame).  Drops the captured programs, like set_source: the next call of each T captures again."""
+        if not self.relative:
+            raise ValueError("Animator.set_driving_initial: this Animator was built with relative=False and has no use for an initial driving frame")
+        assert self.source is not None, "call set_source(source) first"
+        if frame.shape[0] != self.source.shape[0]:
+            raise ValueError(f"Animator.set_driving_initial: one initial driving frame per source ({frame.shape[0]} frames, {self.source.shape[0]} sources)")
+        kp = {k: v for k, v in self.m.encoder(frame).items() if torch.is_tensor(v)}
+        if self.relative_jacobian and "jacobian" not in kp:
+            raise ValueError("Animator(use_relative_jacobian=True): the keypoint detector returns no 'jacobian'")
+        self._kp_init, self._graphs = kp, {}
+        if self.adapt_movement_scale:
+            # normalize_kp's scale, from batch element 0 as there; stays on the device (no .item(): nothing here waits for the host)
+            self._scale = (torch.sqrt(_hull_area(self.kp_s["kp"][0])) / torch.sqrt(_hull_area(kp["kp"][0]))).reshape(1)
 
     def _kp_source(self, T: int) -> dict:
         if T not in self._kp_s_rep:                           # once per T, not per call
@@ -71,6 +105,8 @@ class Animator:
         m = self.m
         T = _frames_per_source(driving.shape[0], self.source.shape[0], "Animator")
         kp_d = m.encoder(driving)
+        if self.relative:                                     # kp_s and kp_init stay at the source batch: the kernel reads entry n // T
+            kp_d = relative_kp(self.kp_s, kp_d, self._kp_init, scale=self._scale, rep=T, use_relative_jacobian=self.relative_jacobian)
         dm = m.dense_motion(self.source, kp_d, self._kp_source(T))
         out, _, _ = m.decoder(self.kp_s["kp"], kp_d["kp"], dm, img=self.img_down, img_full=self.source, source_cache=self.cache, corr=self.corr)
         return out
@@ -78,6 +114,8 @@ class Animator:
     @torch.no_grad()
     def __call__(self, driving: torch.Tensor) -> torch.Tensor:
         assert self.source is not None, "call set_source(source) first"
+        if self.relative and self._kp_init is None:
+            raise RuntimeError("Animator(relative=True): no initial driving frame yet -- call set_driving_initial(frame) or set_source(source, driving_initial)")
         T = _frames_per_source(driving.shape[0], self.source.shape[0], "Animator")
         if not self.use_graph:
             return self._frame(driving)
@@ -144,6 +182,33 @@ def normalize_kp(kp_source, kp_driving, kp_driving_initial, adapt_movement_scale
     return kp_new
 
 
+def relative_kp(kp_source: dict, kp_driving: dict, kp_driving_initial: dict, scale: Optional[torch.Tensor] = None, rep: int = 1,
+                use_relative_jacobian: bool = True) -> dict:
+    """normalize_kp(use_relative_movement=True) as ONE kernel launch (mrfa_kp_relative_fwd) for a clip: kp_driving holds B = Bs rep frames, kp_source and
+    kp_driving_initial the Bs sources / initial frames, frame n reads entry n // rep (no repeated copies).  scale: the movement scale as a one-element
+    fp32 tensor ON THE DEVICE (the kernel reads it there: nothing waits for the host), None for 1.  Every other key of kp_driving passes through;
+    use_relative_jacobian=False passes the driving Jacobian through as well.  Inference only."""
+    ins = [kp_source["kp"], kp_driving["kp"], kp_driving_initial["kp"]]
+    if use_relative_jacobian:
+        for name, kp in (("kp_source", kp_source), ("kp_driving", kp_driving), ("kp_driving_initial", kp_driving_initial)):
+            if "jacobian" not in kp:
+                raise ValueError(f"relative_kp(use_relative_jacobian=True): {name} has no 'jacobian' (a keypoint detector without Jacobians: pass "
+                                 "use_relative_jacobian=False)")
+        ins += [kp_source["jacobian"], kp_driving["jacobian"], kp_driving_initial["jacobian"]]
+    if torch.is_grad_enabled() and any(t.requires_grad for t in ins):
+        raise RuntimeError("relative_kp: the relative keypoints have no backward, not legal in a recording (training) program; normalize_kp is the "
+                           "differentiable torch form")
+    from .engine import Ctx
+    e = Ctx(kp_driving["kp"].device, train=False, record=False)
+    jacs = dict(jd=kp_driving["jacobian"], j0=kp_driving_initial["jacobian"], js=kp_source["jacobian"]) if use_relative_jacobian else {}
+    kp, jac = e.kp_relative(kp_driving["kp"], kp_driving_initial["kp"], kp_source["kp"], scale=scale, rep=rep, **jacs)
+    kp_new = dict(kp_driving)
+    kp_new["kp"] = kp
+    if jac is not None:
+        kp_new["jacobian"] = jac
+    return kp_new
+
+
 def psnr(img1: torch.Tensor, img2: torch.Tensor):
     """20 log10(1 / sqrt(mse)) for images in [0,1].  reference: reconstruction.py:13-19"""
     mse = torch.mean((img1 - img2) ** 2)
@@ -191,31 +256,22 @@ def reconstruction(model: nn.Module, video: torch.Tensor, graph: bool = False, c
 @torch.no_grad()
 def make_animation(model: nn.Module, source: torch.Tensor, driving_video: torch.Tensor, relative: bool = True,
                    adapt_movement_scale: bool = False, graph: bool = False, cache_dtype: torch.dtype = torch.float32, corr: str = "volume",
-                   frames_per_call: int = 1):
+                   frames_per_call: int = 1, initial_frame: int = 0):
     """demo.py:47-73 / animate_ddp.py:88-105: animate ONE source by the motion of a driving clip (B,3,T,H,W); with
-    relative=True the driving keypoints go through normalize_kp against the first driving frame.  frames_per_call: that many frames of the clip run as
-    one batch against the one cached source (a shorter last group at its own size).  Returns (B,3,T,H,W)."""
-    _check_cache_dtype(cache_dtype)
-    check_corr(corr)
+    relative=True the driving keypoints go through normalize_kp against driving frame `initial_frame` (0: the first, as the reference's loop; the index of
+    demo.py:150-157's best frame gives that branch's clip in one pass, since every frame depends on the initial one alone).  frames_per_call: that many
+    frames of the clip run as one batch against the one cached source (a shorter last group at its own size).  graph=True replays one captured program per
+    group size.  One loop over an Animator(relative=relative, ...) in every mode.  Returns (B,3,T,H,W)."""
     fpc = _check_frames_per_call(frames_per_call)
-    m = model.eval()
-    kp_s = m.encoder(source)
-    img_down = m.down(source)
-    cache = m.decoder.encode_source(kp_s["kp"], img_down, source, feature_dtype=cache_dtype)
-    kp_init = m.encoder(driving_video[:, :, 0].contiguous())
     bs, n = source.shape[0], driving_video.shape[2]
-    expanded = {}                                             # group size -> (kp_s, kp_init) expanded to it: at most the full and the tail size
+    if not isinstance(initial_frame, int) or not 0 <= initial_frame < n:
+        raise ValueError(f"initial_frame must be the index of one of the clip's {n} frames, not {initial_frame!r}")
+    anim = Animator(model, graph=graph, cache_dtype=cache_dtype, corr=corr, relative=relative, adapt_movement_scale=adapt_movement_scale)
+    anim.set_source(source, driving_video[:, :, initial_frame].contiguous() if relative else None)
     outs = []
     for t0 in range(0, n, fpc):
         T = min(fpc, n - t0)
-        if T not in expanded:
-            expanded[T] = (_expand_kp(kp_s, T), _expand_kp(kp_init, T))
-        kp_s_T, kp_init_T = expanded[T]
-        kp_d = m.encoder(_clip_group(driving_video, t0, T))
-        kp_n = normalize_kp(kp_s_T, kp_d, kp_init_T, adapt_movement_scale=adapt_movement_scale, use_relative_movement=relative,
-                            use_relative_jacobian=relative)
-        dm = m.dense_motion(source, kp_n, kp_s_T)
-        out, _, _ = m.decoder(kp_s["kp"], kp_n["kp"], dm, img=img_down, img_full=source, source_cache=cache, corr=corr)
+        out = anim(_clip_group(driving_video, t0, T))
         out = out.view(bs, T, *out.shape[1:])
         outs.extend(out[:, j].clone() for j in range(T))
     return torch.stack(outs, dim=2)

@@ -9,6 +9,9 @@
     python tools/bench_animator.py --frames 1 2 4 8 --corr volume direct --rounds 7
                                                                     # a clip of ONE source, T frames per call: the clip Animator (one cached source), the
                                                                     # replicated-source batch-T Animator and the per-frame Animator, alternating round by round
+    python tools/bench_animator.py --relative --frames 1 8 --corr volume direct --rounds 7
+                                                                    # relative motion (normalize_kp against the first driving frame, adapted scale): the graphed
+                                                                    # relative Animator, the graphed absolute Animator and the eager torch loop, alternating
 """
 import argparse
 import copy
@@ -35,6 +38,9 @@ ap.add_argument("--no-graph", action="store_true")
 ap.add_argument("--frames", type=int, nargs="+", default=None, metavar="T",
                 help="frames of one source per call: times Animator calls of T frames against one cached source, against the source replicated T times, and "
                      "per frame (replaces the --batch report)")
+ap.add_argument("--relative", action="store_true",
+                help="relative motion with an adapted movement scale: times the relative Animator, the absolute Animator and the eager loop that calls "
+                     "normalize_kp per group of frames, T = --frames (default 1) frames of one source per call")
 a = ap.parse_args()
 
 dev = torch.device("cuda", 0)
@@ -159,6 +165,60 @@ def clip_report():
                       f"{1e3 / statistics.median(per):.0f} frames/s; device memory held {mem[k]:.1f} MB")
             del steps
 
+
+def relative_report():
+    """one source, T driving frames per call; per corr mode and T three programs in one process: "relative" (Animator(relative=True,
+    adapt_movement_scale=True): the keypoints go through mrfa_kp_relative_fwd inside the frame program), "absolute" (the Animator on the raw driving
+    keypoints) and "eager loop" (the loop make_animation ran before it moved onto the Animator, kept here as the yardstick: normalize_kp as torch launches on
+    repeated keypoints, nothing captured)"""
+    from mrfa_amd.infer import _expand_kp, normalize_kp
+    model = build_model()
+    frames_list = a.frames or [1]
+    src = det_uniform("ba/src", (1, 3, a.size, a.size), 0, 1).to(dev)
+    drv = det_uniform("ba/clip", (max(frames_list) + 1, 3, a.size, a.size), 0, 1).to(dev)
+    first, drv = drv[:1].contiguous(), drv[1:]
+    for corr in a.corr:
+        kp_s, img_down, kp_init = model.encoder(src), model.down(src), model.encoder(first)
+        cache = model.decoder.encode_source(kp_s["kp"], img_down, src)
+        for T in frames_list:
+            frames = drv[:T].contiguous()
+            rel = Animator(model, graph=not a.no_graph, corr=corr, relative=True, adapt_movement_scale=True)
+            rel.set_source(src, first)
+            ab = Animator(model, graph=not a.no_graph, corr=corr)
+            ab.set_source(src)
+            kp_s_T, kp_init_T = _expand_kp(kp_s, T), _expand_kp(kp_init, T)
+
+            def eager_loop():
+                kp_n = normalize_kp(kp_s_T, model.encoder(frames), kp_init_T, adapt_movement_scale=True, use_relative_movement=True, use_relative_jacobian=True)
+                dm = model.dense_motion(src, kp_n, kp_s_T)
+                return model.decoder(kp_s["kp"], kp_n["kp"], dm, img=img_down, img_full=src, source_cache=cache, corr=corr)[0]
+            steps = {"relative": lambda: rel(frames), "absolute": lambda: ab(frames), "eager loop": eager_loop}
+            d = (steps["relative"]().clone() - eager_loop()).abs()
+            times = {k: [] for k in steps}
+            for fn in steps.values():
+                for _ in range(3):
+                    fn()
+            for _ in range(a.rounds):
+                for k, fn in steps.items():                   # the three alternate round by round: same box, same minute
+                    times[k].append(timed(fn))
+            print(f"{a.size}^2 corr={corr} T={T}: relative Animator vs eager loop output max |diff| {d.max().item():.3e} mean {d.mean().item():.3e}")
+            for k, ts in times.items():
+                per = [t / T for t in ts]
+                print(f"{a.size}^2 corr={corr} T={T}: {k:10s} per frame {statistics.median(per):.3f} ms (median of {len(per)}, {min(per):.3f} - {max(per):.3f}), "
+                      f"{1e3 / statistics.median(per):.0f} frames/s")
+            med = {k: statistics.median(ts) / T for k, ts in times.items()}
+            spread = (max(times["absolute"]) - min(times["absolute"])) / T
+            print(f"{a.size}^2 corr={corr} T={T}: relative - absolute {med['relative'] - med['absolute']:+.3f} ms per frame (the absolute rounds spread over "
+                  f"{spread:.3f} ms); eager loop / relative {med['eager loop'] / med['relative']:.2f}x")
+            del steps, rel, ab
+
+
+if a.relative:
+    if a.frames and min(a.frames) < 1:
+        ap.error("--frames: T >= 1")
+    with torch.no_grad():
+        relative_report()
+    sys.exit(0)
 
 if a.frames:
     if min(a.frames) < 1:
