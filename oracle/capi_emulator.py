@@ -28,6 +28,13 @@ def mat(ptr: int, rows: int, ld: int, cols: int) -> torch.Tensor:
     return torch.as_strided(_flat(ptr, (rows - 1) * ld + cols), (rows, cols), (ld, 1))
 
 
+def bf16_mat(ptr: int, rows: int, ld: int, cols: int) -> torch.Tensor:
+    """[rows, cols] strided bf16 view (row stride ld, in bf16 elements) of host memory at ptr"""
+    n = (rows - 1) * ld + cols
+    flat = torch.frombuffer((C.c_int16 * n).from_address(ptr), dtype=torch.int16).view(torch.bfloat16)
+    return torch.as_strided(flat, (rows, cols), (ld, 1))
+
+
 def nhwc(ptr, N, H, W, ld, Cc) -> torch.Tensor:
     return mat(ptr, N * H * W, ld, Cc).view(N, H, W, Cc) if ld == Cc else \
         torch.as_strided(_flat(ptr, (N * H * W - 1) * ld + Cc), (N, H, W, Cc), (H * W * ld, W * ld, ld, 1))
@@ -215,6 +222,39 @@ class Emulator:
             nhwc(djm, B, H, W, lddj, 4).add_(g[1])
         return 0
 
+    def mrfa_kp_relative_fwd(self, stream, kp_d, jac_d, kp_0, jac_0, kp_s, jac_s, scale, B, rep, K, kp_out, jac_out):
+        """mrfa_amd.infer.normalize_kp(use_relative_movement=True) on the first driving frames and sources repeated rep times (repeat_interleave: frame n
+        reads entry n // rep), with the movement scale handed in as one float in memory instead of being taken from the hulls"""
+        from mrfa_amd.infer import normalize_kp          # plain torch, itself pinned to the reference's recorded values (callers.npz)
+        jacs = [bool(p) for p in (jac_d, jac_0, jac_s, jac_out)]
+        bad = None
+        if not (kp_d and kp_0 and kp_s and kp_out):
+            bad = "null keypoint pointer"
+        elif B < 1 or K < 1 or rep < 1:
+            bad = f"B, K and rep must be >= 1 (B {B}, K {K}, rep {rep})"
+        elif B % rep:
+            bad = f"rep must divide B (B {B}, rep {rep})"
+        elif any(jacs) and not all(jacs):
+            bad = f"the four Jacobian pointers come together or not at all ({sum(jacs)} of 4 given)"
+        elif any(p % 8 for p in (kp_d, kp_0, kp_s, kp_out)) or (all(jacs) and any(p % 16 for p in (jac_d, jac_0, jac_s, jac_out))) or (scale and scale % 4):
+            bad = "keypoints must be 8-byte aligned and Jacobians 16-byte aligned (vector loads and stores)"
+        if bad:
+            self._err = ("kp_relative_fwd: " + bad).encode()
+            return 1
+        Bs = B // rep
+        rd = lambda p, n, *shape: _flat(p, n * K * (4 if len(shape) == 2 else 2)).view(n, K, *shape).clone()
+        kd, k0, ks = {"kp": rd(kp_d, B, 2)}, {"kp": rd(kp_0, Bs, 2)}, {"kp": rd(kp_s, Bs, 2)}
+        if all(jacs):
+            kd["jacobian"], k0["jacobian"], ks["jacobian"] = rd(jac_d, B, 2, 2), rd(jac_0, Bs, 2, 2), rd(jac_s, Bs, 2, 2)
+        ri = lambda kp: {k: v.repeat_interleave(rep, dim=0) for k, v in kp.items()}
+        new = normalize_kp(ri(ks), kd, ri(k0), use_relative_movement=True, use_relative_jacobian=all(jacs))
+        if scale:            # normalize_kp's own line with the scale it would have taken from the hulls: difference, times scale, plus source
+            new["kp"] = (kd["kp"] - ri(k0)["kp"]) * _flat(scale, 1)[0] + ri(ks)["kp"]
+        _flat(kp_out, B * K * 2).view(B, K, 2).copy_(new["kp"])
+        if all(jacs):
+            _flat(jac_out, B * K * 4).view(B, K, 2, 2).copy_(new["jacobian"])
+        return 0
+
     # ---------------------------------------------------------------- K22: training losses
     def mrfa_maxpool2_fwd(self, stream, x, ldx, N, H, W, Cc, y, ldy):
         v = F.max_pool2d(nhwc(x, N, H, W, ldx, Cc).permute(0, 3, 1, 2), 2)
@@ -359,7 +399,7 @@ class Emulator:
 
     # ---------------------------------------------------------------- misc
     def mrfa_version(self):
-        return 9              # MRFA_ABI_VERSION of include/mrfa_hip.h
+        return 11             # MRFA_ABI_VERSION of include/mrfa_hip.h (tests/test_emulator_abi_cpu.py holds the three numbers together)
 
     def mrfa_last_error(self):
         return self._err
@@ -823,6 +863,17 @@ class Emulator:
         nhwc(out, N, Ho, Wo, ldo, Cc).copy_(y.permute(0, 2, 3, 1))
         return 0
 
+    def mrfa_grid_sample_bf16_fwd(self, stream, inp, ldi, in_bstride, in_rep, Hi, Wi, Cc, grid, ldg, N, Ho, Wo, out, ldo, mode):
+        """widens its input (exact) and is then mrfa_grid_sample_fwd"""
+        if Cc % 8 or ldi % 8 or in_bstride % 8 or ldo % 4 or inp % 16 or out % 16:
+            self._err = b"grid_sample_bf16_fwd: needs C % 8 == 0, ldi % 8 == 0, in_bstride % 8 == 0, ldo % 4 == 0 and 16-byte aligned in / out"
+            return 1
+        n_in = (N + in_rep - 1) // in_rep
+        assert in_bstride == Hi * Wi * ldi
+        wide = torch.zeros((n_in * Hi * Wi, ldi), dtype=torch.float32)            # the widened copy, same geometry (counted in fp32 elements)
+        wide[:, :Cc] = bf16_mat(inp, n_in * Hi * Wi, ldi, Cc).float()
+        return self.mrfa_grid_sample_fwd(stream, wide.data_ptr(), ldi, in_bstride, in_rep, Hi, Wi, Cc, grid, ldg, N, Ho, Wo, out, ldo, mode)
+
     def mrfa_warp_frame_reflect(self, stream, inp, N, Cc, H, W, grid, Ho, Wo, out):
         x = _flat(inp, N * Cc * H * W).view(N, Cc, H, W)
         g = _flat(grid, N * Ho * Wo * 2).view(N, Ho, Wo, 2)
@@ -930,6 +981,49 @@ class Emulator:
             mat(dcoords, Q, lddc, 2).add_(gc)
         return 0
 
+    def mrfa_corr_direct_fwd(self, stream, q, ldq, k0, ldk0, k1, ldk1, N, h1, w1, Hs, Ws, D, coords, ldc, radius, scale, out, ldo):
+        """forms both correlation volumes with a matmul (vol_l[n Q + i, j] = scale * sum_c q[n, i, c] k_l[n, j, c]) and is then mrfa_corr_lookup_fwd on them"""
+        nwin = (2 * radius + 1) ** 2
+        bad = None
+        if not 0 <= radius <= 3:
+            bad = "the window's lattice must fit one wave (0 <= radius <= 3)"
+        elif not (q and k0 and k1 and coords and out and N > 0 and h1 > 0 and w1 > 0 and D > 0):
+            bad = "null pointer or non-positive size"
+        elif Hs < 2 or Ws < 2 or Hs % 2 or Ws % 2:
+            bad = "Hs and Ws must be even and >= 2"
+        elif ldc < 2 or ldo < 2 * nwin or min(ldq, ldk0, ldk1) < D:
+            bad = "a leading dimension is below its channel count"
+        elif D % 4 or ldq % 4 or ldk0 % 4 or ldk1 % 4 or q % 16 or k0 % 16 or k1 % 16:
+            bad = "needs D % 4 == 0, ldq / ldk0 / ldk1 % 4 == 0 and 16-byte aligned q / k0 / k1"
+        if bad:
+            self._err = ("corr_direct_fwd: " + bad).encode()
+            return 1
+        Q, S0, S1 = h1 * w1, Hs * Ws, (Hs // 2) * (Ws // 2)
+        qm = mat(q, N * Q, ldq, D).view(N, Q, D)
+        vol0 = (torch.matmul(qm, mat(k0, N * S0, ldk0, D).view(N, S0, D).transpose(1, 2)) * scale).contiguous()
+        vol1 = (torch.matmul(qm, mat(k1, N * S1, ldk1, D).view(N, S1, D).transpose(1, 2)) * scale).contiguous()
+        return self.mrfa_corr_lookup_fwd(stream, vol0.data_ptr(), vol1.data_ptr(), Hs, Ws, coords, ldc, N * Q, radius, out, ldo)
+
+    def mrfa_corr_direct_rep_fwd(self, stream, q, ldq, k0, ldk0, k1, ldk1, N, k_rep, h1, w1, Hs, Ws, D, coords, ldc, radius, scale, out, ldo):
+        """mrfa_corr_direct_fwd on keys repeated k_rep times (repeat_interleave: query image n reads key image n // k_rep), with its argument refusals and
+        the two of its own"""
+        if k_rep < 1 or N % k_rep:
+            self._err = f"corr_direct_rep_fwd: k_rep >= 1 must divide N (N {N}, k_rep {k_rep})".encode()
+            return 1
+        # corr_direct_fwd's refusals, asked of the caller's own key pointers and leading dimensions before any key is read: its words in its order
+        # (radius; null / non-positive; Hs, Ws; leading dimensions; D % 4, ld % 4, alignment)
+        if (not 0 <= radius <= 3 or not (q and k0 and k1 and coords and out and N > 0 and h1 > 0 and w1 > 0 and D > 0) or Hs < 2 or Ws < 2 or Hs % 2 or Ws % 2
+                or ldc < 2 or ldo < 2 * (2 * radius + 1) ** 2 or min(ldq, ldk0, ldk1) < D or D % 4 or ldq % 4 or ldk0 % 4 or ldk1 % 4
+                or q % 16 or k0 % 16 or k1 % 16):
+            rc = self.mrfa_corr_direct_fwd(stream, q, ldq, k0, ldk0, k1, ldk1, N, h1, w1, Hs, Ws, D, coords, ldc, radius, scale, out, ldo)
+            assert rc != 0                                    # (no key was read: corr_direct_fwd refuses these arguments whatever the keys hold)
+            return rc
+        Nk, S0, S1 = N // k_rep, Hs * Ws, (Hs // 2) * (Ws // 2)
+        r0 = mat(k0, Nk * S0, ldk0, D).view(Nk, S0, D).repeat_interleave(k_rep, dim=0).contiguous()       # dense: ld = D, D % 4 == 0
+        r1 = mat(k1, Nk * S1, ldk1, D).view(Nk, S1, D).repeat_interleave(k_rep, dim=0).contiguous()
+        assert r0.data_ptr() % 16 == 0 and r1.data_ptr() % 16 == 0
+        return self.mrfa_corr_direct_fwd(stream, q, ldq, r0.data_ptr(), D, r1.data_ptr(), D, N, h1, w1, Hs, Ws, D, coords, ldc, radius, scale, out, ldo)
+
     # ---------------------------------------------------------------- layout / elementwise
     def mrfa_nchw_to_nhwc(self, stream, src, dst, ldd, N, Cc, H, W, acc):
         s = _flat(src, N * Cc * H * W).view(N, Cc, H, W).permute(0, 2, 3, 1)
@@ -947,6 +1041,15 @@ class Emulator:
         s = mat(x, rows, ldx, Cc) * mul
         d = mat(y, rows, ldy, Cc)
         d.copy_(d + s if acc else s)
+        return 0
+
+    def mrfa_cast_bf16(self, stream, x, ldx, rows, Cc, y, ldy):
+        """`tensor.to(torch.bfloat16)`: round to nearest, ties to even"""
+        if Cc % 8 or ldx % 8 or ldy % 8 or x % 16 or y % 16:
+            self._err = b"cast_bf16: needs C % 8 == 0, ldx % 8 == 0, ldy % 8 == 0 and 16-byte aligned pointers"
+            return 1
+        if rows:
+            bf16_mat(y, rows, ldy, Cc).copy_(mat(x, rows, ldx, Cc).to(torch.bfloat16))
         return 0
 
     def mrfa_timestamp(self, stream, dst):

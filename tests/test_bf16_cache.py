@@ -1,7 +1,7 @@
 """The bf16 source-feature cache of the animation loop: RaftFlow.encode_source(feature_dtype=torch.bfloat16) / Animator(cache_dtype=torch.bfloat16),
 the two kernels behind it (mrfa_cast_bf16, mrfa_grid_sample_bf16_fwd) and the dtype rule of engine.View.
 
-Module parity (CPU through the emulator subclass of tests/emu_bf16.py, and on the GPU): the expected value is the reference-pinned oracle run on THE SAME
+Module parity (CPU through the ABI emulator, tests/emu.py, and on the GPU): the expected value is the reference-pinned oracle run on THE SAME
 ROUNDED PYRAMID -- the bf16 cache is read back, widened (exact) and handed to the oracle in place of its own generator_encode -- so everything downstream of
 the pyramid is the same program on both sides and the project's module-parity bound applies for its usual reason: max |diff| <= 1e-3, mean <= 1e-4
 (tests/test_parity_gpu.py::_cmp).  That the rounded pyramid itself is right is the cast test (bit-identical round-to-nearest-even) plus the existing fp32
@@ -17,7 +17,7 @@ from mrfa_amd import engine, hip
 from mrfa_amd.modules import RaftFlow
 from oracle import mrfa_oracle as O
 from tests import cases
-from tests.emu_bf16 import cache_pyramid_bytes, cache_pyramid_nchw, emulated_hip_bf16, oracle_pyramid
+from tests.emu import cache_pyramid_bytes, cache_pyramid_nchw, emulated_hip, oracle_pyramid
 from tests.sample_grids import gs_grid as _gs_grid
 from tests.test_oracle_golden import raft_inputs
 
@@ -58,10 +58,10 @@ def _raft_parity(size, b, prior_only, dev, tag):
     assert s.shape == (b, 1, size, (6 if prior_only else 7) * size)
 
 
-# ------------------------------------------------------------------------------------------------------------------ CPU, through the emulator subclass
+# ------------------------------------------------------------------------------------------------------------------ CPU, through the emulator
 def test_encode_source_bf16_storages_and_bytes():
     size, b = 64, 2
-    with emulated_hip_bf16():
+    with emulated_hip():
         rf, _ = _raft(size, False, "cpu")
         kp_s, _, _, img, img_full = raft_inputs(size, b, "bf16/enc")
         c32 = rf.encode_source(kp_s, img, img_full)
@@ -81,7 +81,7 @@ def test_encode_source_bf16_storages_and_bytes():
 
 
 def test_bf16_view_never_reaches_an_fp32_kernel():
-    with emulated_hip_bf16():
+    with emulated_hip():
         e = engine.Ctx(torch.device("cpu"), train=False, record=False)
         x = e.new(1, 4, 4, 16)
         x.tensor().copy_(torch.randn(1, 4, 4, 16))
@@ -127,7 +127,7 @@ def _dry_model():
 def test_animator_cache_dtype_argument():
     from mrfa_amd.infer import Animator, make_animation, reconstruction
     from mrfa_amd.utils.prng import det_uniform
-    with emulated_hip_bf16():
+    with emulated_hip():
         m = _dry_model()
         for bad in (torch.float16, torch.float64, None):
             with pytest.raises(ValueError, match="torch.float32 or torch.bfloat16"):
@@ -156,7 +156,7 @@ def test_animator_cache_dtype_argument():
 
 @pytest.mark.parametrize("prior_only", [False, True])
 def test_raft_flow_from_bf16_cache_through_emulator(prior_only):
-    with emulated_hip_bf16():
+    with emulated_hip():
         _raft_parity(64, 2, prior_only, "cpu", "bf16/raft64")
 
 

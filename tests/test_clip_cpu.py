@@ -1,4 +1,4 @@
-"""A clip against one cached source on the CPU, through the emulator subclass of tests/emu_clip.py (mrfa_corr_direct_rep_fwd = the parent's
+"""A clip against one cached source on the CPU, through the ABI emulator (tests/emu.py; mrfa_corr_direct_rep_fwd =
 mrfa_corr_direct_fwd on repeated keys): B = Bs T driving frames, frame n of source n // T, against the same program on a physically replicated source
 (repeat_interleave(T) of source, kp_s and cache); what the default paths hand the library; what is refused."""
 import pytest
@@ -7,8 +7,9 @@ import torch
 from mrfa_amd import engine, hip
 from mrfa_amd.engine import Storage, View
 from mrfa_amd.modules import RaftFlow
+from oracle.capi_emulator import Emulator
 from tests import cases
-from tests.emu_clip import EmulatorClip, emulated_hip_clip
+from tests.emu import emulated_hip
 from tests.test_oracle_golden import raft_inputs
 
 SIZE, BS, T = 64, 2, 3
@@ -46,7 +47,7 @@ def replicate_cache(cache: dict, t: int) -> dict:
 
 
 def test_emulator_rep_entry_refuses_its_two_bad_arguments_and_the_parents():
-    emu = EmulatorClip()
+    emu = Emulator()
     assert emu.mrfa_version() == 11 == hip.ABI_VERSION
     assert "mrfa_corr_direct_rep_fwd" in hip.EXPORTED_SYMBOLS
     q, k0, k1 = torch.randn(4 * 6, 8), torch.randn(16 * 2, 8), torch.randn(4 * 2, 8)
@@ -61,7 +62,7 @@ def test_emulator_rep_entry_refuses_its_two_bad_arguments_and_the_parents():
 
 
 def test_ctx_corr_direct_k_rep_equals_repeated_keys():
-    with emulated_hip_clip(counting=True) as lib:
+    with emulated_hip(counting=True) as lib:
         e = engine.Ctx(torch.device("cpu"), train=False, record=False)
         g = torch.Generator().manual_seed(5)
         q, k0, co = e.new(6, 3, 5, 16), e.new(2, 6, 4, 16), e.new(6, 3, 5, 2)
@@ -92,7 +93,7 @@ def test_ctx_corr_direct_k_rep_equals_repeated_keys():
 def test_raft_flow_clip_equals_replicated_source(corr, prior_only):
     """corr="direct" (and the prior-only program, which has no correlation): every emulated operation has the same shape in both runs -> torch.equal.
     corr="volume": the volume matmul has another batch shape (Bs problems of T Q rows against B of Q) -> the golden gate."""
-    with emulated_hip_clip():
+    with emulated_hip():
         rf = _raft(prior_only)
         kp_s, kp_d, dmo, img, img_full = clip_inputs()
         with torch.no_grad():
@@ -113,7 +114,7 @@ def test_raft_flow_clip_equals_replicated_source(corr, prior_only):
 
 @pytest.mark.parametrize("corr", ["direct", "volume"])
 def test_same_batch_reaches_only_the_parents_entry_points(corr):
-    with emulated_hip_clip(counting=True) as lib:
+    with emulated_hip(counting=True) as lib:
         rf = _raft()
         kp_s, kp_d, dmo, img, img_full = raft_inputs(SIZE, BS, "clip/src")
         with torch.no_grad():
@@ -129,7 +130,7 @@ def test_same_batch_reaches_only_the_parents_entry_points(corr):
 
 
 def test_clip_reaches_the_rep_entry_and_in_rep():
-    with emulated_hip_clip(counting=True) as lib:
+    with emulated_hip(counting=True) as lib:
         rf = _raft()
         kp_s, kp_d, dmo, img, img_full = clip_inputs()
         with torch.no_grad():
@@ -144,7 +145,7 @@ def test_clip_reaches_the_rep_entry_and_in_rep():
 
 
 def test_batch_mismatch_is_refused():
-    with emulated_hip_clip(counting=True) as lib:
+    with emulated_hip(counting=True) as lib:
         rf = _raft()
         kp_s, kp_d, dmo, img, img_full = clip_inputs()
         with torch.no_grad():
@@ -183,7 +184,7 @@ def _gate(a, b, what):
 def test_callers_frames_per_call():
     from mrfa_amd.infer import Animator, make_animation, reconstruction
     from tests.test_bf16_cache import _dry_model
-    with emulated_hip_clip(counting=True) as lib:
+    with emulated_hip(counting=True) as lib:
         m = _dry_model()
         src, clip = _clips(4)                                                  # groups of 3: one full group and a tail of 1
         for bad in (0, -1):
@@ -220,7 +221,7 @@ def test_one_source_many_frames():
     """Bs = 1 (the demo loop's case): a repeat of ONE image is a stride-0 expansion until it is copied"""
     from mrfa_amd.infer import Animator
     from tests.test_bf16_cache import _dry_model
-    with emulated_hip_clip():
+    with emulated_hip():
         m = _dry_model()
         src, clip = _clips(2)
         an = Animator(m, corr="direct")

@@ -1,5 +1,5 @@
-"""RaftFlow.forward(corr="direct") on the CPU, through the emulator subclass of tests/emu_corr_direct.py (mrfa_corr_direct_fwd = matmul volumes + the
-parent's lookup): parity with the reference-pinned oracle, which entry points the two modes reach, and what the argument refuses."""
+"""RaftFlow.forward(corr="direct") on the CPU, through the ABI emulator (tests/emu.py; mrfa_corr_direct_fwd = matmul volumes +
+mrfa_corr_lookup_fwd): parity with the reference-pinned oracle, which entry points the two modes reach, and what the argument refuses."""
 import importlib.util
 import os
 
@@ -9,8 +9,9 @@ import torch
 from mrfa_amd import engine, hip
 from mrfa_amd.modules import RaftFlow
 from oracle import mrfa_oracle as O
+from oracle.capi_emulator import Emulator
 from tests import cases
-from tests.emu_corr_direct import EmulatorCorrDirect, emulated_hip_corr_direct
+from tests.emu import emulated_hip
 from tests.test_oracle_golden import raft_inputs
 
 SIZE, B = 64, 2
@@ -34,18 +35,16 @@ def _traced(rf, ins, cache=False, **kw):
     """the ABI calls of one forward as tools/abi_trace.py writes them (entry point, every scalar argument and struct field, weight hashes)"""
     T = _abi_trace()
     lines = []
-    with T.traced_hip(lines) as lib:
-        lib.emu = EmulatorCorrDirect()
-        with torch.no_grad():
-            if cache:
-                kw["source_cache"] = rf.encode_source(ins[0], ins[3], ins[4])
-                del lines[:]
-            out = rf(*ins, **kw)
+    with T.traced_hip(lines), torch.no_grad():
+        if cache:
+            kw["source_cache"] = rf.encode_source(ins[0], ins[3], ins[4])
+            del lines[:]
+        out = rf(*ins, **kw)
     return lines, out
 
 
-def test_emulator_subclass_reports_version_11_and_refuses_bad_arguments():
-    emu = EmulatorCorrDirect()
+def test_emulator_reports_version_11_and_refuses_bad_corr_direct_arguments():
+    emu = Emulator()
     assert emu.mrfa_version() == 11 == hip.ABI_VERSION
     q, k0, k1 = torch.randn(4, 8), torch.randn(16, 8), torch.randn(4, 8)
     c, out = torch.zeros(4, 2), torch.full((4, 98), 7.0)
@@ -59,7 +58,7 @@ def test_emulator_subclass_reports_version_11_and_refuses_bad_arguments():
 
 
 def test_ctx_corr_direct_is_the_lookup_on_matmul_volumes_and_refuses_a_tape():
-    with emulated_hip_corr_direct():
+    with emulated_hip():
         e = engine.Ctx(torch.device("cpu"), train=False, record=False)
         g = torch.Generator().manual_seed(3)
         q, k0, co = e.new(2, 3, 5, 16), e.new(2, 6, 4, 16), e.new(2, 3, 5, 2)
@@ -81,7 +80,7 @@ def test_ctx_corr_direct_is_the_lookup_on_matmul_volumes_and_refuses_a_tape():
 @pytest.mark.parametrize("cache", [False, True])
 def test_raft_flow_direct_through_emulator_vs_oracle(cache):
     """the tolerance of the emulator leg tests/test_wiring_cpu.py::test_raft_flow_through_emulator: max |diff| < 1e-4"""
-    with emulated_hip_corr_direct():
+    with emulated_hip():
         rf, sd = _raft()
         ins = raft_inputs(SIZE, B, "g3/raft64")
         kp_s, kp_d, dmo, img, img_full = ins
@@ -106,7 +105,7 @@ def _is_volume_gemm(line, rf):
 def test_direct_builds_no_volume_where_volume_builds_eight(cache):
     """what each mode hands the library.  (That corr="volume" is the PARENT commit's call list is not something one tree can test: it is recorded,
     parent against new, in profiles/corr_direct_identity.txt.)"""
-    with emulated_hip_corr_direct():
+    with emulated_hip():
         rf, _ = _raft()
         ins = raft_inputs(SIZE, B, "g3/raft64")
         ins = (ins[0], ins[1], ins[2], ins[3], ins[4])
@@ -132,7 +131,7 @@ def test_direct_builds_no_volume_where_volume_builds_eight(cache):
 
 
 def test_corr_argument_is_checked():
-    with emulated_hip_corr_direct(counting=True) as lib:
+    with emulated_hip(counting=True) as lib:
         rf, _ = _raft()
         kp_s, kp_d, dmo, img, img_full = raft_inputs(SIZE, B, "g3/raft64")
         with torch.no_grad():
@@ -161,7 +160,7 @@ def test_animator_corr_argument():
     from mrfa_amd.infer import Animator, make_animation, reconstruction
     from mrfa_amd.utils.prng import det_uniform
     from tests.test_bf16_cache import _dry_model
-    with emulated_hip_corr_direct(counting=True) as lib:
+    with emulated_hip(counting=True) as lib:
         m = _dry_model()
         for bad in ("bogus", None, "Direct"):
             with pytest.raises(ValueError, match="volume.*direct"):

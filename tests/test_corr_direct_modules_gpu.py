@@ -11,7 +11,7 @@ import torch
 from mrfa_amd.modules import RaftFlow
 from oracle import mrfa_oracle as O
 from tests import cases
-from tests.emu_bf16 import cache_pyramid_nchw, oracle_pyramid
+from tests.emu import cache_pyramid_nchw, oracle_pyramid
 from tests.test_oracle_golden import raft_inputs
 
 pytestmark = pytest.mark.gpu

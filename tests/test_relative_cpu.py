@@ -1,4 +1,4 @@
-"""Relative-motion animation on the CPU, through the emulator subclass of tests/emu_relative.py (mrfa_kp_relative_fwd = normalize_kp on repeated first
+"""Relative-motion animation on the CPU, through the ABI emulator (tests/emu.py; mrfa_kp_relative_fwd = normalize_kp on repeated first
 frames and sources, the scale handed in): the entry against the reference's recorded normalize_kp, rep against physical repeats, what it refuses, the relative
 Animator against the reference's recorded animation, and which Animator reaches the entry how often."""
 import os
@@ -9,8 +9,9 @@ import torch
 
 from mrfa_amd import hip
 from mrfa_amd.infer import Animator, _hull_area, relative_kp
+from oracle.capi_emulator import Emulator
 from tests import cases
-from tests.emu_relative import EmulatorRelative, emulated_hip_relative
+from tests.emu import emulated_hip
 
 
 def _clone(kp):
@@ -35,8 +36,8 @@ def test_entry_reproduces_the_references_normalize_kp(golden_dir):
     g = dict(np.load(os.path.join(golden_dir, "callers.npz")))
     ks, kd, k0 = cases.keypoints("g6/ks", 2), cases.keypoints("g6/kd", 2), cases.keypoints("g6/k0", 2)
     before = [_clone(t) for t in (ks, kd, k0)]
-    assert "mrfa_kp_relative_fwd" in hip.EXPORTED_SYMBOLS and EmulatorRelative().mrfa_version() == hip.ABI_VERSION
-    with emulated_hip_relative(counting=True) as lib:
+    assert "mrfa_kp_relative_fwd" in hip.EXPORTED_SYMBOLS and Emulator().mrfa_version() == hip.ABI_VERSION
+    with emulated_hip(counting=True) as lib:
         for adapt in (False, True):
             scale = (torch.sqrt(_hull_area(ks["kp"][0])) / torch.sqrt(_hull_area(k0["kp"][0]))).reshape(1) if adapt else None
             for rel, relj in ((False, False), (True, False), (True, True)):
@@ -55,7 +56,7 @@ def test_entry_reproduces_the_references_normalize_kp(golden_dir):
 
 @pytest.mark.parametrize("jac", [True, False])
 def test_rep_equals_physically_repeated_inputs(jac):
-    emu, rep = EmulatorRelative(), 3
+    emu, rep = Emulator(), 3
     kd, k0, ks = cases.keypoints("rel/rep/kd", 6, 15), cases.keypoints("rel/rep/k0", 2, 15), cases.keypoints("rel/rep/ks", 2, 15)
     scale = torch.tensor([0.37])
     rc, kp, jo = _entry(emu, kd, k0, ks, scale, rep=rep, jac=jac)
@@ -70,7 +71,7 @@ def test_rep_equals_physically_repeated_inputs(jac):
 
 
 def test_entry_refuses_bad_arguments_and_leaves_the_outputs_untouched():
-    emu = EmulatorRelative()
+    emu = Emulator()
     kd, k0, ks = cases.keypoints("rel/bad/kd", 6), cases.keypoints("rel/bad/k0", 2), cases.keypoints("rel/bad/ks", 2)
     rc, kp, jo = _entry(emu, kd, k0, ks, rep=3)
     assert rc == 0 and not (kp == 7).any() and not (jo == 7).any()
@@ -88,7 +89,7 @@ def test_entry_refuses_bad_arguments_and_leaves_the_outputs_untouched():
 
 def test_wrapper_refuses_a_missing_jacobian_and_a_recording_context():
     kd, k0, ks = cases.keypoints("rel/w/kd", 2), cases.keypoints("rel/w/k0", 2), cases.keypoints("rel/w/ks", 2)
-    with emulated_hip_relative(counting=True) as lib:
+    with emulated_hip(counting=True) as lib:
         for i in range(3):
             kps = [dict(ks), dict(kd), dict(k0)]
             del kps[i]["jacobian"]
@@ -110,7 +111,7 @@ def test_wrapper_refuses_a_missing_jacobian_and_a_recording_context():
 def test_relative_animator_needs_an_initial_frame():
     from tests.test_bf16_cache import _dry_model
     from tests.test_clip_cpu import _clips
-    with emulated_hip_relative():
+    with emulated_hip():
         m = _dry_model()
         src, clip = _clips(2)
         an = Animator(m, relative=True)
@@ -133,7 +134,7 @@ def test_make_animation_is_one_animator_loop_that_reaches_the_entry():
     from mrfa_amd.infer import make_animation
     from tests.test_bf16_cache import _dry_model
     from tests.test_clip_cpu import _clips, _gate
-    with emulated_hip_relative(counting=True) as lib:
+    with emulated_hip(counting=True) as lib:
         m = _dry_model()
         src, clip = _clips(3)
         del lib.calls[:]
@@ -154,17 +155,16 @@ def test_make_animation_is_one_animator_loop_that_reaches_the_entry():
 
 
 def test_a_library_without_the_entry_runs_the_torch_form_and_says_so():
-    """tests/emu_clip.py's emulator stands for a version-11 library built before the entry: hip.has() is False, Ctx.kp_relative warns once per process and
+    """the emulator without the entry stands for a version-11 library built before it: hip.has() is False, Ctx.kp_relative warns once per process and
     computes normalize_kp's own operations (bit for bit its result on repeated inputs); a misaligned view is copied, not refused"""
     from mrfa_amd import engine
     from mrfa_amd.infer import normalize_kp
-    from tests.emu_clip import emulated_hip_clip
     kd, k0, ks = cases.keypoints("rel/old/kd", 6), cases.keypoints("rel/old/k0", 2), cases.keypoints("rel/old/ks", 2)
     scale = torch.tensor([0.37])
     ri = lambda d: {k: v.repeat_interleave(3, dim=0) for k, v in d.items()}
     ref = normalize_kp(ri(ks), kd, ri(k0), use_relative_movement=True, use_relative_jacobian=True)
     ref_kp = (kd["kp"] - ri(k0)["kp"]) * scale + ri(ks)["kp"]
-    with emulated_hip_clip():
+    with emulated_hip(without=("mrfa_kp_relative_fwd",)):
         assert not hip.has("mrfa_kp_relative_fwd")
         engine.Ctx._warned_no_kp_relative = False
         with pytest.warns(RuntimeWarning, match="no mrfa_kp_relative_fwd"):
@@ -174,7 +174,7 @@ def test_a_library_without_the_entry_runs_the_torch_form_and_says_so():
         with warnings.catch_warnings():
             warnings.simplefilter("error")                                            # once per process
             assert torch.equal(relative_kp(ks, kd, k0, rep=3)["kp"], ref["kp"])
-    with emulated_hip_relative(counting=True) as lib:
+    with emulated_hip(counting=True) as lib:
         assert hip.has("mrfa_kp_relative_fwd")
         flat = torch.zeros(6 * 10 * 4 + 1)
         odd = dict(kd, jacobian=flat[1:].view(6, 10, 2, 2).copy_(kd["jacobian"]))     # 4 bytes past a 16-byte boundary
@@ -192,7 +192,7 @@ def _launches(lib):
 def test_which_animator_reaches_the_entry_and_how_often():
     from tests.test_bf16_cache import _dry_model
     from tests.test_clip_cpu import BS, _clips, _gate
-    with emulated_hip_relative(counting=True) as lib:
+    with emulated_hip(counting=True) as lib:
         m = _dry_model()
         src, clip = _clips(3)
         group = lambda T: clip[:, :, :T].permute(0, 2, 1, 3, 4).reshape(BS * T, *clip.shape[1:2], *clip.shape[3:]).contiguous()
@@ -224,7 +224,7 @@ def test_relative_animator_clip_against_the_references_animation(golden_dir):
     _check_against_reference_callers, the three frames in ONE call (T = 3), against the reference's recorded demo.make_animation at that test's tolerance"""
     from tests.test_callers import _dropin_model
     g = np.load(os.path.join(golden_dir, "dropin_fomm.npz"))
-    with emulated_hip_relative(counting=True) as lib:
+    with emulated_hip(counting=True) as lib:
         m = _dropin_model("fomm", "cpu")
         src = cases.images("dropin/src", 1, 256)
         drv = [cases.images(f"dropin/drv{t}", 1, 256) for t in range(3)]

@@ -70,9 +70,9 @@ def test_kp_relative_kernel_against_float64(B, rep, K):
     either count absorbs every second-order term ((1 + e)^-1 and products of roundings: with entries <= 2 and |det| >= 0.25, (|ad| + |bc|) / |det| <= 32 and
     u 33^2 << 1):   |out - ref| <= u (8 + 4 (|ad| + |bc|) / |det|) M / |det|.
     A contraction of a multiplication and an addition into one fused operation removes a rounding and never adds one.  Nothing here is measured.
-    Also: two runs are bit-identical, nothing outside the outputs is written, the inputs are not written, and the CPU specification (tests/emu_relative.py)
+    Also: two runs are bit-identical, nothing outside the outputs is written, the inputs are not written, and the CPU specification (oracle/capi_emulator.py)
     lies within the same bounds of the kernel."""
-    from tests.emu_relative import EmulatorRelative
+    from oracle.capi_emulator import Emulator
     ins = _inputs(B, rep, K, seed=1000 * B + 10 * rep + K)
     dev_in = [t.to(DEV) for t in ins]
     kd, k0, ks, jd, j0, js = (t.double() for t in ins)
@@ -98,7 +98,7 @@ def test_kp_relative_kernel_against_float64(B, rep, K):
             # the specification on the same numbers
             e_kp, e_jac = torch.full((B, K, 2), CANARY), torch.full((B, K, 2, 2), CANARY)
             q = lambda t, on=True: t.data_ptr() if on and t is not None else None
-            assert EmulatorRelative().mrfa_kp_relative_fwd(0, q(ins[0]), q(ins[3], jac), q(ins[1]), q(ins[4], jac), q(ins[2]), q(ins[5], jac), q(scale), B, rep,
+            assert Emulator().mrfa_kp_relative_fwd(0, q(ins[0]), q(ins[3], jac), q(ins[1]), q(ins[4], jac), q(ins[2]), q(ins[5], jac), q(scale), B, rep,
                                                            K, q(e_kp), q(e_jac, jac)) == 0
             assert ((kp.double() - e_kp.double()).abs() <= kp_bound).all()
             if jac:
@@ -216,7 +216,7 @@ def test_make_animation_graph_really_replays(monkeypatch):
 
 def test_default_make_animation_reaches_the_kernel(monkeypatch):
     """make_animation(relative=True) without a graph -- its default -- goes through mrfa_kp_relative_fwd of the built library, once per group of frames"""
-    from tests.emu_corr_direct import Counting
+    from tests.emu import Counting
     m, src, drv = _scene("fomm")
     assert hip.has("mrfa_kp_relative_fwd")
     proxy = Counting(hip.lib())

@@ -58,11 +58,9 @@ def programs(T, lines):
 
 
 def main(out_path):
-    from tests.emu_corr_direct import EmulatorCorrDirect
     T = _abi_trace()
     lines = []
-    with T.traced_hip(lines) as lib, torch.no_grad():
-        lib.emu = EmulatorCorrDirect()
+    with T.traced_hip(lines), torch.no_grad():
         programs(T, lines)
     with open(out_path, "w") as f:
         f.write("\n".join(lines) + "\n")
