@@ -1829,6 +1829,36 @@ class Ctx:
         self._chk(self.L.mrfa_kp_relative_fwd(self.s, p(kd), p(jd), p(k0), p(j0), p(ks), p(js), p(scale), B, rep, K, p(kp_out), p(jac_out)), "kp_relative_fwd")
         return kp_out, jac_out
 
+    def kp_pose_dist(self, kd, ks, rep: int = 1, state: Optional[torch.Tensor] = None, want_dist: bool = True, want_area: bool = False):
+        """Pose distance of B = Bs rep driving frames kd (B,K,2) to their sources ks (Bs,K,2), frame n against source n // rep, in one launch
+        (mrfa_kp_pose_dist, include/mrfa_hip_ext.h): centre the keypoints, divide by the square root of their convex-hull area, sum the squared differences
+        (demo.py:75-98 on keypoints).  state: None or infer.pose_state(Bs, device), the running argmin of a clip, updated IN PLACE on the device (frame j of
+        this call has clip index frames_seen + j).  -> (dist (B) or None, hull area (B) or None), fresh tensors.  Inference only; 3 <= K <= 64.
+        The entry is not part of include/mrfa_hip.h's table: a library built before it existed has no such kernel, and there is no torch form."""
+        if self.record:
+            raise RuntimeError("Ctx.kp_pose_dist: the pose distance has no backward, not legal in a recording (training) program")
+        kd, ks = (self._aligned(self._cf(t), 8) for t in (kd, ks))
+        if kd.dim() != 3 or ks.dim() != 3 or kd.shape[2] != 2 or ks.shape[2] != 2:
+            raise ValueError(f"kp_pose_dist: keypoints are (B,K,2) and (Bs,K,2), not {tuple(kd.shape)} and {tuple(ks.shape)}")
+        B, K = kd.shape[0], kd.shape[1]
+        if not isinstance(rep, int) or rep < 1 or B != ks.shape[0] * rep or ks.shape[1] != K:
+            raise ValueError(f"kp_pose_dist: source n // rep for frame n ({B} frames of {K} keypoints, {ks.shape[0]} sources of {ks.shape[1]}, rep {rep!r})")
+        if not 3 <= K <= 64:
+            raise ValueError(f"kp_pose_dist: a hull needs 3 <= K <= 64 keypoints (K {K})")
+        if state is None and not (want_dist or want_area):
+            raise ValueError("kp_pose_dist: no state, no distances and no areas asked for: nothing to compute")
+        if state is not None and not (state.dtype == torch.int32 and tuple(state.shape) == (B // rep, 4) and state.is_contiguous() and state.device == kd.device):
+            raise ValueError(f"kp_pose_dist: state is a contiguous int32 ({B // rep},4) tensor on the keypoints' device (infer.pose_state), not "
+                             f"{state.dtype} {tuple(state.shape)} on {state.device}")
+        if not hip.has("mrfa_kp_pose_dist"):
+            raise RuntimeError(f"the loaded version-{hip.ABI_VERSION} library has no mrfa_kp_pose_dist (it was built before the entry was added, "
+                               "include/mrfa_hip_ext.h) and the pose distance has no other form: rebuild it with `python -m mrfa_amd.build --force`")
+        dist = torch.empty(B, dtype=torch.float32, device=kd.device) if want_dist else None
+        area = torch.empty(B, dtype=torch.float32, device=kd.device) if want_area else None
+        p = lambda t: None if t is None else t.data_ptr()
+        self._chk(self.L.mrfa_kp_pose_dist(self.s, p(kd), p(ks), B, rep, K, p(dist), p(area), p(state)), "kp_pose_dist")
+        return dist, area
+
     @staticmethod
     def _aligned(t: Optional[torch.Tensor], nbytes: int) -> Optional[torch.Tensor]:
         return t if t is None or t.data_ptr() % nbytes == 0 else t.clone()

@@ -225,6 +225,11 @@ EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 # entries added to ABI version 11 without moving the number (include/mrfa_hip.h): a version-11 library built before one of them lacks it.  lib() loads such a
 # library; the one caller of the entry (engine.Ctx.kp_relative) looks the symbol up with has() and says what it does without it
 ADDITIVE_SYMBOLS = ("mrfa_kp_relative_fwd",)
+# entries of include/mrfa_hip_ext.h: a table of their own, outside _SIGNATURES / EXPORTED_SYMBOLS / ADDITIVE_SYMBOLS (those three mirror include/mrfa_hip.h).
+# lib() binds the ones the library exports and skips the others; the one caller of each asks has() and says that the library has to be rebuilt
+_EXT_SIGNATURES = {
+    "mrfa_kp_pose_dist": ([_V, _V, _V, _I, _I, _I, _V, _V, _V], C.c_int),
+}
 LN_SLOTS = 16          # MRFA_LN_SLOTS
 RESIZE_SUM_TERMS = 4   # MRFA_RESIZE_SUM_TERMS
 ABI_VERSION = 11       # MRFA_ABI_VERSION of include/mrfa_hip.h: the struct layouts above mirror THAT header; lib() refuses any other library
@@ -258,6 +263,11 @@ def lib():
                 continue
             fn.argtypes = argtypes
             fn.restype = restype
+        for name, (argtypes, restype) in _EXT_SIGNATURES.items():
+            fn = getattr(L, name, None)
+            if fn is not None:
+                fn.argtypes = argtypes
+                fn.restype = restype
         if L.mrfa_version() != ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH} speaks ABI version {L.mrfa_version()}, this binding was written against {ABI_VERSION} "
                                "(include/mrfa_hip.h MRFA_ABI_VERSION): rebuild the library (`python -m mrfa_amd.build --force`)")
@@ -291,7 +301,7 @@ def mfma_mode() -> str:
 
 
 def has(name: str) -> bool:
-    """whether the loaded library exports `name` (one of ADDITIVE_SYMBOLS; every other entry is there or lib() raised)"""
+    """whether the loaded library exports `name` (one of ADDITIVE_SYMBOLS or _EXT_SIGNATURES; every other entry is there or lib() raised)"""
     return getattr(lib(), name, None) is not None
 
 

@@ -209,6 +209,102 @@ def relative_kp(kp_source: dict, kp_driving: dict, kp_driving_initial: dict, sca
     return kp_new
 
 
+_INF_BITS = 0x7F800000          # +inf as the int32 that shares its bits
+
+
+def pose_state(bs: int, device) -> torch.Tensor:
+    """a fresh running argmin for bs sources (mrfa_kp_pose_dist's state, include/mrfa_hip_ext.h): (bs,4) int32 rows {best distance as fp32 bits = +inf,
+    best index 0, frames seen 0, pad}.  Column 1 is the answer; a clip with no finite distance leaves it at 0, as the reference's loop does."""
+    st = torch.zeros(bs, 4, dtype=torch.int32, device=device)
+    st[:, 0] = _INF_BITS
+    return st
+
+
+class BestFrameSearch:
+    """demo.py:75-98 (find_best_frame) for the clips of Bs sources, on the model's own keypoints: the driving frame whose pose -- keypoints centred and
+    divided by the square root of their hull area -- is closest to the source's.  set_source(source), add(frames) group after group, result().  add is the
+    keypoint detector plus ONE launch (mrfa_kp_pose_dist) that also keeps the running argmin and the frame count on the device: nothing waits for the host
+    until result().  graph=True keeps one captured program per group size T (the frame offset lives in the state, so one program serves every group); as
+    with Animator(graph=True), do not run the model's modules eagerly between two replays of a capture."""
+
+    def __init__(self, model: nn.Module, graph: bool = False):
+        self.m = model.eval()
+        self.use_graph = graph
+        self.kp_s: Optional[torch.Tensor] = None
+        self.state: Optional[torch.Tensor] = None
+        self._graphs: dict = {}                               # T -> (graph, static driving frames)
+
+    @torch.no_grad()
+    def set_source(self, source: torch.Tensor):
+        """the keypoints of the Bs sources and a fresh state; drops the captured programs (they hold the old tensors' addresses)"""
+        self.kp_s = self.m.encoder(source)["kp"]
+        self.state = pose_state(source.shape[0], source.device)
+        self._graphs = {}
+
+    def reset(self):
+        """a new clip against the same sources: the state is refilled in place, the captured programs stay valid"""
+        assert self.state is not None, "call set_source(source) first"
+        self.state.copy_(pose_state(self.state.shape[0], self.state.device))
+
+    @torch.no_grad()
+    def _group(self, frames: torch.Tensor, state: torch.Tensor, want_dist: bool):
+        from .engine import Ctx
+        T = _frames_per_source(frames.shape[0], self.kp_s.shape[0], "BestFrameSearch")
+        kp_d = self.m.encoder(frames)["kp"]
+        return Ctx(kp_d.device, train=False, record=False).kp_pose_dist(kp_d, self.kp_s, rep=T, state=state, want_dist=want_dist)[0]
+
+    @torch.no_grad()
+    def add(self, frames: torch.Tensor):
+        """the next Bs T frames of the clips, frame n of source n // T (any T >= 1, groups of different sizes in any order)"""
+        assert self.state is not None, "call set_source(source) first"
+        T = _frames_per_source(frames.shape[0], self.kp_s.shape[0], "BestFrameSearch")
+        if not self.use_graph:
+            self._group(frames, self.state, False)
+            return
+        if T not in self._graphs:                             # capture once per T, as Animator.__call__ does
+            from . import graph_replay_safe
+            graph_replay_safe("BestFrameSearch(graph=True)")
+            drv = frames.clone()
+            eager = self._group(drv, pose_state(self.state.shape[0], self.state.device), True).clone()      # packs / tables outside the graph; a scratch state
+            torch.cuda.synchronize()
+            kept = self.state.clone()                         # the check replays below advance the state: put it back, whatever they find
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                dist = self._group(drv, self.state, True)
+            try:
+                for k in range(3):
+                    g.replay()
+                    torch.cuda.synchronize()
+                    # the detector's split-K sums differ run to run in their last bits; a mis-ordered graph reads stale or zero keypoints
+                    if not (torch.isfinite(dist) == torch.isfinite(eager)).all() or not torch.allclose(dist, eager, rtol=1e-3, atol=1e-6, equal_nan=True):
+                        raise RuntimeError(f"BestFrameSearch: hipGraph replay {k} differs from the eager distances ({dist.tolist()} vs {eager.tolist()})")
+            finally:
+                self.state.copy_(kept)
+            self._graphs[T] = (g, drv)
+        g, drv = self._graphs[T]
+        drv.copy_(frames)
+        g.replay()
+
+    def result(self) -> list:
+        """the index of the best frame of each source's clip: the one read of the host"""
+        assert self.state is not None, "call set_source(source) first"
+        return self.state[:, 1].tolist()
+
+
+@torch.no_grad()
+def find_best_frame(model: nn.Module, source: torch.Tensor, driving_video: torch.Tensor, frames_per_call: int = 1, graph: bool = False) -> list:
+    """demo.py:75-98 on a driving clip (B,3,T,H,W): per source the index of the frame whose normalised keypoints are closest to the source's.  The keypoints
+    are the model's K, not 68 face landmarks, so the index can differ from the reference's on the same clip.  frames_per_call frames per group (a shorter last
+    group at its own size); one host read, at the end."""
+    fpc = _check_frames_per_call(frames_per_call)
+    search = BestFrameSearch(model, graph=graph)
+    search.set_source(source)
+    n = driving_video.shape[2]
+    for t0 in range(0, n, fpc):
+        search.add(_clip_group(driving_video, t0, min(fpc, n - t0)))
+    return search.result()
+
+
 def psnr(img1: torch.Tensor, img2: torch.Tensor):
     """20 log10(1 / sqrt(mse)) for images in [0,1].  reference: reconstruction.py:13-19"""
     mse = torch.mean((img1 - img2) ** 2)
@@ -256,18 +352,29 @@ def reconstruction(model: nn.Module, video: torch.Tensor, graph: bool = False, c
 @torch.no_grad()
 def make_animation(model: nn.Module, source: torch.Tensor, driving_video: torch.Tensor, relative: bool = True,
                    adapt_movement_scale: bool = False, graph: bool = False, cache_dtype: torch.dtype = torch.float32, corr: str = "volume",
-                   frames_per_call: int = 1, initial_frame: int = 0):
+                   frames_per_call: int = 1, initial_frame=0):
     """demo.py:47-73 / animate_ddp.py:88-105: animate ONE source by the motion of a driving clip (B,3,T,H,W); with
     relative=True the driving keypoints go through normalize_kp against driving frame `initial_frame` (0: the first, as the reference's loop; the index of
-    demo.py:150-157's best frame gives that branch's clip in one pass, since every frame depends on the initial one alone).  frames_per_call: that many
+    demo.py:150-157's best frame gives that branch's clip in one pass, since every frame depends on the initial one alone).  initial_frame: an index for
+    every source, a sequence of B indices (one per source), or "best": find_best_frame(model, source, driving_video) with the same frames_per_call and
+    graph, each source measured from its own best frame (relative=False has no initial frame and searches for none).  frames_per_call: that many
     frames of the clip run as one batch against the one cached source (a shorter last group at its own size).  graph=True replays one captured program per
     group size.  One loop over an Animator(relative=relative, ...) in every mode.  Returns (B,3,T,H,W)."""
     fpc = _check_frames_per_call(frames_per_call)
     bs, n = source.shape[0], driving_video.shape[2]
-    if not isinstance(initial_frame, int) or not 0 <= initial_frame < n:
-        raise ValueError(f"initial_frame must be the index of one of the clip's {n} frames, not {initial_frame!r}")
+    if isinstance(initial_frame, str) and initial_frame == "best":
+        initial_frame = find_best_frame(model, source, driving_video, frames_per_call=fpc, graph=graph) if relative else 0
+    per_source = isinstance(initial_frame, (list, tuple))
+    indices = list(initial_frame) if per_source else [initial_frame]
+    if (per_source and len(indices) != bs) or not all(isinstance(i, int) and 0 <= i < n for i in indices):
+        raise ValueError(f"initial_frame must be the index of one of the clip's {n} frames, a sequence of {bs} such indices (one per source) or \"best\", "
+                         f"not {initial_frame!r}")
     anim = Animator(model, graph=graph, cache_dtype=cache_dtype, corr=corr, relative=relative, adapt_movement_scale=adapt_movement_scale)
-    anim.set_source(source, driving_video[:, :, initial_frame].contiguous() if relative else None)
+    if per_source:                                            # Animator.set_driving_initial takes one frame per source: frame indices[s] of source s
+        initial = torch.stack([driving_video[s, :, i] for s, i in enumerate(indices)], dim=0)
+    else:
+        initial = driving_video[:, :, initial_frame].contiguous()
+    anim.set_source(source, initial if relative else None)
     outs = []
     for t0 in range(0, n, fpc):
         T = min(fpc, n - t0)

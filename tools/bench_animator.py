@@ -12,6 +12,9 @@
     python tools/bench_animator.py --relative --frames 1 8 --corr volume direct --rounds 7
                                                                     # relative motion (normalize_kp against the first driving frame, adapted scale): the graphed
                                                                     # relative Animator, the graphed absolute Animator and the eager torch loop, alternating
+    python tools/bench_animator.py --best-frame --frames 8 --rounds 7
+                                                                    # the best-frame search (BestFrameSearch.add: keypoint detector + mrfa_kp_pose_dist) per frame,
+                                                                    # captured and eager, beside the keypoint detector alone on the same groups, alternating
 """
 import argparse
 import copy
@@ -41,6 +44,9 @@ ap.add_argument("--frames", type=int, nargs="+", default=None, metavar="T",
 ap.add_argument("--relative", action="store_true",
                 help="relative motion with an adapted movement scale: times the relative Animator, the absolute Animator and the eager loop that calls "
                      "normalize_kp per group of frames, T = --frames (default 1) frames of one source per call")
+ap.add_argument("--best-frame", action="store_true",
+                help="the best-frame search of a clip of one source, T = --frames (default 8) frames per call: BestFrameSearch.add captured and eager, and the "
+                     "keypoint detector alone on the same groups captured and eager, alternating round by round")
 a = ap.parse_args()
 
 dev = torch.device("cuda", 0)
@@ -212,6 +218,65 @@ def relative_report():
                   f"{spread:.3f} ms); eager loop / relative {med['eager loop'] / med['relative']:.2f}x")
             del steps, rel, ab
 
+
+def best_frame_report():
+    """one source, T driving frames per call; four programs in one process: "search graph" / "search eager" (BestFrameSearch.add: the keypoint detector on
+    the group plus ONE mrfa_kp_pose_dist launch that keeps the running argmin on the device) and "detector graph" / "detector eager" (the keypoint detector
+    alone on the same group: what a search cannot do without).  Nothing reads the device inside a timed window; result() is read once per search, after it."""
+    from mrfa_amd.infer import BestFrameSearch
+    model = build_model()
+    src = det_uniform("ba/src", (1, 3, a.size, a.size), 0, 1).to(dev)
+    for T in a.frames or [8]:
+        groups = [det_uniform(f"ba/best{g}", (T, 3, a.size, a.size), 0, 1).to(dev) for g in range(4)]
+        searches = {}
+        for graph in (True, False):
+            sr = BestFrameSearch(model, graph=graph)
+            sr.set_source(src)
+            for g in groups:
+                sr.add(g)
+            searches[graph] = sr
+        found = {graph: (sr.result(), sr.state[:, 2].tolist()) for graph, sr in searches.items()}
+        print(f"{a.size}^2 T={T}, {model.prior} keypoint detector: a clip of {4 * T} frames in 4 groups: best frame {found[True][0]} captured, {found[False][0]} eager; frames seen {found[True][1]}")
+        assert found[True] == found[False], found
+        from mrfa_amd import graph_replay_safe
+        graph_replay_safe("bench_animator --best-frame")      # (as every capture of the project; the search legs ask through BestFrameSearch)
+        static = groups[0].clone()
+        model.encoder(static)
+        torch.cuda.synchronize()
+        gd = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gd):
+            model.encoder(static)
+        it = iter(range(1 << 30))
+        nxt = lambda: groups[next(it) % 4]
+
+        def detector_graph():
+            static.copy_(nxt())
+            gd.replay()
+        steps = {"search graph": lambda: searches[True].add(nxt()), "search eager": lambda: searches[False].add(nxt()),
+                 "detector graph": detector_graph, "detector eager": lambda: model.encoder(nxt())}
+        times = {k: [] for k in steps}
+        for fn in steps.values():
+            for _ in range(3):
+                fn()
+        for _ in range(a.rounds):
+            for k, fn in steps.items():                       # the four alternate round by round: same box, same minute
+                times[k].append(timed(fn, n=200))             # a call is under a millisecond: 200 of them per window
+        for k, ts in times.items():
+            per = [t / T for t in ts]
+            print(f"{a.size}^2 T={T}: {k:14s} per call {summary(ts)}; per frame {statistics.median(per):.4f} ms ({min(per):.4f} - {max(per):.4f})")
+        med = {k: statistics.median(ts) / T for k, ts in times.items()}
+        for mode in ("graph", "eager"):
+            spread = (max(times[f"detector {mode}"]) - min(times[f"detector {mode}"])) / T
+            print(f"{a.size}^2 T={T}: search - detector, {mode}: {med[f'search {mode}'] - med[f'detector {mode}']:+.4f} ms per frame (the detector rounds spread "
+                  f"over {spread:.4f} ms)")
+
+
+if a.best_frame:
+    if a.frames and min(a.frames) < 1:
+        ap.error("--frames: T >= 1")
+    with torch.no_grad():
+        best_frame_report()
+    sys.exit(0)
 
 if a.relative:
     if a.frames and min(a.frames) < 1:
