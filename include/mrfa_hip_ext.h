@@ -1,9 +1,9 @@
-/* libmrfa_hip.so: entries whose CPU specification lives beside their tests (tests/emu_ext.py), not in the ABI emulator.
+/* libmrfa_hip.so: entries whose CPU specification lives beside their tests (tests/emu_ext.py, tests/emu_metrics.py), not in the ABI emulator.
  *
  * include/mrfa_hip.h is one table with the ctypes binding (mrfa_amd/hip.py: _SIGNATURES) and the emulator: an entry declared there has to appear in
  * all three at once.  An entry declared HERE is bound from the binding's second table (hip._EXT_SIGNATURES), looked up with hip.has() by its one caller,
- * and specified by tests/emu_ext.py::ExtEmulator.  The ABI version of mrfa_hip.h does not move for it: a library without the entry loads, and the caller
- * says that the library has to be rebuilt.
+ * and specified by tests/emu_ext.py::ExtEmulator or a subclass of it (tests/emu_metrics.py::MetricsEmulator).  The ABI version of mrfa_hip.h does not
+ * move for it: a library without the entry loads, and the caller says that the library has to be rebuilt.
  */
 #ifndef MRFA_HIP_EXT_H
 #define MRFA_HIP_EXT_H
@@ -32,6 +32,29 @@ extern "C" {
  *   3 <= K <= 64; kp_d and kp_s 8-byte aligned (float2 loads), the outputs and the state 4-byte aligned.  One workgroup (one wave) per source, no atomics:
  *   two runs on the same input are bit-identical.  Returns 0, or nonzero with mrfa_last_error() set before anything is written. */
 int mrfa_kp_pose_dist(void* stream, const float* kp_d, const float* kp_s, int B, int rep, int K, float* dist_out, float* area_out, void* state);
+
+/* Full-reference metrics of a clip, per frame: L1, MSE and SSIM of pred (N,C,H,W) against target (N,C,H,W), frame n against frame n, both contiguous
+ * fp32 (reconstruction.py:52-70 reports L1 and PSNR per frame; PSNR is 20 log10(1 / sqrt(mse)), the caller's one line).  Inference only.
+ *
+ *   out (N,4): out[n] = {l1, mse, ssim, 0};  l1 = mean |p - t| and mse = mean (p - t)^2 over C H W.
+ *   ssim (Wang et al. 2004, data range 1): window of 11 taps g_i = exp(-(i - 5)^2 / 4.5) / sum, computed in float64 and rounded to fp32 -- those eleven
+ *   fp32 numbers are the definition --, separable and "valid" (no padding: (H - 10) x (W - 10) windows per channel); under it mu_x, mu_y, E[x^2], E[y^2],
+ *   E[xy]; s_xx = E[x^2] - mu_x^2, s_yy and s_xy likewise, not clamped; C1 = 0.01^2, C2 = 0.03^2;
+ *     S = (2 mu_x mu_y + C1)(2 s_xy + C2) / ((mu_x^2 + mu_y^2 + C1)(s_xx + s_yy + C2));   ssim = mean of S over channels and windows.
+ *   want_ssim == 0: ssim is written as 0 (never NaN) and no window is computed; any H, W >= 1.  want_ssim != 0 needs min(H, W) >= 11.
+ *   Non-finite inputs propagate through the sums of the frames (and windows) that hold them; the entry does not classify them.
+ *   The kernels work in fp32 on tiles of MRFA_METRICS_TILE_H x MRFA_METRICS_TILE_W pixels (second moments on x - 0.5 and y - 0.5: the variances do not
+ *   move, the means get the 0.5 back), no fp32 addition chain longer than 16; the tiles' partial sums are added in float64 in a fixed order, divided by
+ *   the counts and rounded once.  No atomics: two runs on the same input are bit-identical.  Any H and W: every load is one fp32.
+ *   workspace: mrfa_frame_metrics_workspace(N, C, H, W) bytes of scratch (24 per tile, channel and frame; < 0 if a dimension is < 1 or the tiles exceed
+ *   one grid), written by every call, whatever it held before.
+ *   pred, target and out 4-byte aligned, the workspace 8-byte aligned.  Returns 0, or nonzero with mrfa_last_error() set before anything is written: a null
+ *   pointer, a dimension < 1, a workspace smaller than asked for, want_ssim with min(H, W) < 11, a misaligned pointer. */
+#define MRFA_METRICS_TILE_H 32
+#define MRFA_METRICS_TILE_W 32
+long long mrfa_frame_metrics_workspace(int N, int C, int H, int W);
+int mrfa_frame_metrics(void* stream, const float* pred, const float* target, int N, int C, int H, int W, int want_ssim, void* workspace,
+                       long long workspace_bytes, float* out);
 
 #ifdef __cplusplus
 }

@@ -308,6 +308,9 @@ BRANCH_STREAMS = os.environ.get("MRFA_BRANCH_STREAMS", "1") != "0"        # (kep
 # (batch statistics, scale / shift, the backward's sums; `groups` momentum updates of the running statistics in group order; num_batches_tracked += groups);
 # everything else has no cross-sample coupling.  Half / a third of the launches of a latency-bound chain, twice / three times the rows per launch.
 STAT_GROUPS = 1
+# (TH, TW) of mrfa_frame_metrics (MRFA_METRICS_TILE_H / _W of include/mrfa_hip_ext.h): one workgroup per tile, channel and frame; a tile owns the SSIM windows
+# whose top-left corner lies in it.  Exported for the tests, which place their shapes on the seams, and for the specification's workspace size
+METRICS_TILE = (32, 32)
 
 
 class stat_groups:
@@ -1858,6 +1861,43 @@ class Ctx:
         p = lambda t: None if t is None else t.data_ptr()
         self._chk(self.L.mrfa_kp_pose_dist(self.s, p(kd), p(ks), B, rep, K, p(dist), p(area), p(state)), "kp_pose_dist")
         return dist, area
+
+    _metrics_ws: dict = {}                             # (device, stream, N, C, H, W) -> workspace of mrfa_frame_metrics, one per shape seen
+
+    def frame_metrics(self, pred: torch.Tensor, target: torch.Tensor, want_ssim: bool = True) -> torch.Tensor:
+        """L1, MSE and SSIM of frame n of pred (N,C,H,W) against frame n of target in one entry call (mrfa_frame_metrics, include/mrfa_hip_ext.h: two
+        launches on this stream, nothing waits for the host) -> a fresh (N,4) fp32 tensor on the frames' device, rows {l1, mse, ssim, 0}; ssim is 0 with
+        want_ssim=False and needs min(H, W) >= 11 otherwise.  Both operands contiguous fp32 on one device: nothing is copied or converted here.
+        Inference only.  The entry is not part of include/mrfa_hip.h's table: a library built before it existed has no such kernel, and there is no torch
+        form."""
+        if self.record:
+            raise RuntimeError("Ctx.frame_metrics: the frame metrics have no backward, not legal in a recording (training) program")
+        for name, t in (("pred", pred), ("target", target)):
+            if not torch.is_tensor(t) or t.dim() != 4 or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"frame_metrics: {name} is a contiguous fp32 (N,C,H,W) tensor, not "
+                                 f"{(t.dtype, tuple(t.shape), 'contiguous' if t.is_contiguous() else 'strided') if torch.is_tensor(t) else type(t).__name__}")
+        if pred.shape != target.shape or pred.device != target.device or pred.device != torch.device(self.dev):
+            raise ValueError(f"frame_metrics: frame n of pred against frame n of target on this context's device ({tuple(pred.shape)} on {pred.device}, "
+                             f"{tuple(target.shape)} on {target.device}, context on {self.dev})")
+        N, C, H, W = pred.shape
+        if min(N, C, H, W) < 1:
+            raise ValueError(f"frame_metrics: N, C, H and W must be >= 1, not {tuple(pred.shape)}")
+        if want_ssim and min(H, W) < 11:
+            raise ValueError(f"frame_metrics: SSIM needs one 11 x 11 window, min(H, W) >= 11 ({H} x {W}); want_ssim=False gives L1 and MSE alone")
+        if not (hip.has("mrfa_frame_metrics") and hip.has("mrfa_frame_metrics_workspace")):
+            raise RuntimeError(f"the loaded version-{hip.ABI_VERSION} library has no mrfa_frame_metrics (it was built before the entry was added, "
+                               "include/mrfa_hip_ext.h) and the frame metrics have no other form: rebuild it with `python -m mrfa_amd.build --force`")
+        key = (pred.device, self.s, N, C, H, W)
+        ws = Ctx._metrics_ws.get(key)
+        if ws is None:
+            need = self.L.mrfa_frame_metrics_workspace(N, C, H, W)
+            if need < 0:
+                raise ValueError(f"frame_metrics: {N} x {C} planes of {H} x {W} are more tiles than one launch takes")
+            ws = Ctx._metrics_ws[key] = torch.empty(need // 8, dtype=torch.float64, device=pred.device)
+        out = torch.empty(N, 4, dtype=torch.float32, device=pred.device)
+        self._chk(self.L.mrfa_frame_metrics(self.s, pred.data_ptr(), target.data_ptr(), N, C, H, W, int(bool(want_ssim)), ws.data_ptr(),
+                                            ws.numel() * 8, out.data_ptr()), "frame_metrics")
+        return out
 
     @staticmethod
     def _aligned(t: Optional[torch.Tensor], nbytes: int) -> Optional[torch.Tensor]:

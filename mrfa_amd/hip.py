@@ -229,6 +229,8 @@ ADDITIVE_SYMBOLS = ("mrfa_kp_relative_fwd",)
 # lib() binds the ones the library exports and skips the others; the one caller of each asks has() and says that the library has to be rebuilt
 _EXT_SIGNATURES = {
     "mrfa_kp_pose_dist": ([_V, _V, _V, _I, _I, _I, _V, _V, _V], C.c_int),
+    "mrfa_frame_metrics_workspace": ([_I, _I, _I, _I], C.c_longlong),
+    "mrfa_frame_metrics": ([_V, _V, _V, _I, _I, _I, _I, _I, _V, _L, _V], C.c_int),
 }
 LN_SLOTS = 16          # MRFA_LN_SLOTS
 RESIZE_SUM_TERMS = 4   # MRFA_RESIZE_SUM_TERMS

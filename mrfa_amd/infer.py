@@ -313,6 +313,47 @@ def psnr(img1: torch.Tensor, img2: torch.Tensor):
     return 20 * torch.log10(1.0 / torch.sqrt(mse))
 
 
+def _psnr_of_mse(mse):
+    """infer.psnr on float64 numpy mean squared errors: 20 log10(1 / sqrt(mse)), inf where mse == 0"""
+    import numpy as np
+    with np.errstate(divide="ignore"):
+        return np.where(mse == 0, np.inf, 20.0 * np.log10(1.0 / np.sqrt(mse)))
+
+
+def ssim(img1: torch.Tensor, img2: torch.Tensor) -> torch.Tensor:
+    """SSIM of image n of img1 against image n of img2, both (N,C,H,W) contiguous fp32 in [0,1] on one device -> (N,) fp32 on that device: Wang et al.
+    2004 with an 11-tap Gaussian window (sigma 1.5), no padding, C1 = 0.01^2, C2 = 0.03^2, the mean over channels and windows (include/mrfa_hip_ext.h,
+    mrfa_frame_metrics).  The reference declares a loss_list_ssim and never fills it (reconstruction.py:43)."""
+    from .engine import Ctx
+    return Ctx(img1.device, train=False, record=False).frame_metrics(img1, img2, want_ssim=True)[:, 2]
+
+
+class ClipMetrics:
+    """The full-reference metrics of a clip, kept on the device: add(pred, target) group after group, result() once.  add is ONE entry call
+    (mrfa_frame_metrics) for the N frames of a group; its (N,4) rows {l1, mse, ssim, 0} stay on the device in the order added, and nothing waits for the
+    host until result().  ssim=False leaves the SSIM windows out (its column is 0) and takes frames of any size; with SSIM, min(H, W) >= 11."""
+
+    def __init__(self, ssim: bool = True):
+        self.want_ssim = bool(ssim)
+        self.rows: list = []
+
+    @torch.no_grad()
+    def add(self, pred: torch.Tensor, target: torch.Tensor):
+        """frame n of pred (N,C,H,W) against frame n of target, both contiguous fp32 on one device"""
+        from .engine import Ctx
+        self.rows.append(Ctx(pred.device, train=False, record=False).frame_metrics(pred, target, want_ssim=self.want_ssim))
+
+    def __len__(self) -> int:
+        return sum(r.shape[0] for r in self.rows)
+
+    def result(self) -> dict:
+        """the one read of the host: {'l1', 'mse', 'psnr', 'ssim'}, float64 numpy arrays with one value per frame added, in that order.
+        psnr = 20 log10(1 / sqrt(mse)), inf where mse == 0 (infer.psnr, reconstruction.py:13-19)"""
+        import numpy as np
+        rows = torch.cat(self.rows, dim=0).cpu().numpy().astype(np.float64) if self.rows else np.zeros((0, 4))
+        return {"l1": rows[:, 0].copy(), "mse": rows[:, 1].copy(), "psnr": _psnr_of_mse(rows[:, 1]), "ssim": rows[:, 2].copy()}
+
+
 def _check_frames_per_call(frames_per_call) -> int:
     if not isinstance(frames_per_call, int) or frames_per_call < 1:
         raise ValueError(f"frames_per_call must be an integer >= 1, not {frames_per_call!r}")
@@ -327,15 +368,24 @@ def _clip_group(video: torch.Tensor, t0: int, T: int) -> torch.Tensor:
 
 @torch.no_grad()
 def reconstruction(model: nn.Module, video: torch.Tensor, graph: bool = False, cache_dtype: torch.dtype = torch.float32, corr: str = "volume",
-                   frames_per_call: int = 1):
+                   frames_per_call: int = 1, metrics: str = "host"):
     """The reference's reconstruction loop (reconstruction.py:52-70) on one clip: source = frame 0, driving = every frame t,
     metrics mean|out - driving| and PSNR per frame.  video: (B,3,T,H,W) in [0,1].  The source is fixed for the whole clip, so
     the source half of the path is computed once (Animator).  frames_per_call: that many frames of the clip run as one batch against the one cached
-    source (a shorter last group at its own size).  Returns {'prediction': (B,3,T,H,W), 'l1': [T], 'psnr': [T]}."""
+    source (a shorter last group at its own size).
+    metrics="host": torch operations per frame, three host reads each.  Returns {'prediction': (B,3,T,H,W), 'l1': [T], 'psnr': [T]}.
+    metrics="device": one ClipMetrics.add per group of frames (row s T + j of a group: source s, frame t0 + j) and ONE host read at the end of the clip;
+    SSIM comes with it (min(H, W) >= 11).  Returns 'prediction' as above; 'l1', 'psnr', 'ssim': [T] floats -- the mean over sources of the per-source l1
+    (the host path's number up to rounding), the PSNR of the mean per-source mse (likewise) and the mean per-source SSIM --; and 'per_source':
+    {'l1', 'mse', 'psnr', 'ssim'}, float64 numpy arrays (B,T)."""
     fpc = _check_frames_per_call(frames_per_call)
+    if metrics not in ("host", "device"):
+        raise ValueError(f"reconstruction: metrics must be \"host\" or \"device\", not {metrics!r}")
     anim = Animator(model, graph=graph, cache_dtype=cache_dtype, corr=corr)
     anim.set_source(video[:, :, 0].contiguous())
     bs = video.shape[0]
+    if metrics == "device":
+        return _reconstruction_device_metrics(anim, video, fpc)
     preds, l1, ps = [], [], []
     for t0 in range(0, video.shape[2], fpc):
         T = min(fpc, video.shape[2] - t0)
@@ -347,6 +397,28 @@ def reconstruction(model: nn.Module, video: torch.Tensor, graph: bool = False, c
             l1.append(float(torch.abs(out - driving).mean()))
             ps.append(float(psnr(driving, out)))
     return {"prediction": torch.stack(preds, dim=2), "l1": l1, "psnr": ps}
+
+
+def _reconstruction_device_metrics(anim: Animator, video: torch.Tensor, fpc: int) -> dict:
+    """reconstruction(metrics="device") behind its set_source: the clip in groups, the metrics of each group from one entry call on the Animator's output
+    where it lies (before the next call overwrites a captured program's output: the same stream), one host read after the last group"""
+    import numpy as np
+    bs, n = video.shape[0], video.shape[2]
+    cm, preds, sizes = ClipMetrics(ssim=True), [], []
+    for t0 in range(0, n, fpc):
+        T = min(fpc, n - t0)
+        driving = _clip_group(video, t0, T)
+        outs = anim(driving).contiguous()
+        cm.add(outs, driving)
+        preds.append(outs.view(bs, T, *outs.shape[1:]).clone())
+        sizes.append(T)
+    res = cm.result()
+    per_source, row = {}, np.cumsum([0] + [bs * T for T in sizes])
+    for name, v in res.items():                               # rows of group g: (bs, T_g) -> (bs, n), the groups side by side
+        per_source[name] = np.concatenate([v[row[g]:row[g + 1]].reshape(bs, T) for g, T in enumerate(sizes)], axis=1)
+    return {"prediction": torch.cat(preds, dim=1).permute(0, 2, 1, 3, 4).contiguous(),
+            "l1": per_source["l1"].mean(axis=0).tolist(), "psnr": _psnr_of_mse(per_source["mse"].mean(axis=0)).tolist(),
+            "ssim": per_source["ssim"].mean(axis=0).tolist(), "per_source": per_source}
 
 
 @torch.no_grad()
