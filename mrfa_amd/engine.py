@@ -313,6 +313,18 @@ STAT_GROUPS = 1
 METRICS_TILE = (32, 32)
 
 
+class FrameTile(NamedTuple):
+    """one tile of Ctx.frames_to_u8 (mrfa_u8_tile of include/mrfa_hip_ext.h): image n of src (N,3,H,W) fp32 goes to dst[n, y0:y0+H, x0:x0+W, :]; kp (N,K,2)
+    with colors (K,3) draws discs of `radius` pixels, border sets the tile's first and last column to 255"""
+    src: torch.Tensor
+    y0: int = 0
+    x0: int = 0
+    kp: Optional[torch.Tensor] = None
+    radius: float = 0.0
+    colors: Optional[torch.Tensor] = None
+    border: bool = False
+
+
 class stat_groups:
     """with stat_groups(g): programs started inside treat their batch as g statistic groups of N / g consecutive samples"""
 
@@ -1897,6 +1909,98 @@ class Ctx:
         out = torch.empty(N, 4, dtype=torch.float32, device=pred.device)
         self._chk(self.L.mrfa_frame_metrics(self.s, pred.data_ptr(), target.data_ptr(), N, C, H, W, int(bool(want_ssim)), ws.data_ptr(),
                                             ws.numel() * 8, out.data_ptr()), "frame_metrics")
+        return out
+
+    @staticmethod
+    def _what(t) -> str:
+        return f"{t.dtype} {tuple(t.shape)} {'contiguous' if t.is_contiguous() else 'strided'} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+
+    def _need_frames_entry(self, name: str):
+        if not hip.has(name):
+            raise RuntimeError(f"the loaded version-{hip.ABI_VERSION} library has no {name} (it was built before the entry was added, "
+                               "include/mrfa_hip_ext.h) and the byte frames have no other form: rebuild it with `python -m mrfa_amd.build --force`")
+
+    def frames_from_u8(self, u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """uint8 frames (N,H,W,Cin), Cin in {1,3,4}, contiguous on this context's device -> fp32 (N,3,H,W) = byte * fl32(1/255) in one launch
+        (mrfa_frames_from_u8, include/mrfa_hip_ext.h): grey goes to all three planes, alpha is dropped.  out: a contiguous fp32 (N,3,H,W) tensor on the
+        same device to write into (a captured program's static input), else a fresh one.  Inference only.  The entry is not part of include/mrfa_hip.h's
+        table: a library built before it existed has no such kernel, and there is no torch form."""
+        if self.record:
+            raise RuntimeError("Ctx.frames_from_u8: the byte conversion has no backward, not legal in a recording (training) program")
+        if not torch.is_tensor(u8) or u8.dtype != torch.uint8 or u8.dim() != 4 or not u8.is_contiguous() or u8.device != torch.device(self.dev):
+            raise ValueError(f"frames_from_u8: frames are a contiguous uint8 (N,H,W,C) tensor on {self.dev}, not {self._what(u8)}")
+        N, H, W, Cin = u8.shape
+        if min(N, H, W) < 1 or Cin not in (1, 3, 4):
+            raise ValueError(f"frames_from_u8: N, H, W >= 1 and C in (1, 3, 4) -- grey, RGB, RGBA --, not {tuple(u8.shape)}")
+        if out is None:
+            out = torch.empty((N, 3, H, W), dtype=torch.float32, device=u8.device)
+        elif not (torch.is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == (N, 3, H, W) and out.is_contiguous() and out.device == u8.device):
+            raise ValueError(f"frames_from_u8: out is a contiguous fp32 {(N, 3, H, W)} tensor on {u8.device}, not {self._what(out)}")
+        self._need_frames_entry("mrfa_frames_from_u8")
+        self._chk(self.L.mrfa_frames_from_u8(self.s, u8.data_ptr(), N, H, W, Cin, out.data_ptr()), "frames_from_u8")
+        return out
+
+    def frames_to_u8(self, tiles: Sequence[FrameTile], out: Optional[torch.Tensor] = None, rounding: str = "nearest") -> torch.Tensor:
+        """fp32 frames -> uint8 (N,Hd,Wd,3) in one launch (mrfa_frames_to_u8, include/mrfa_hip_ext.h).  tiles: 1..8 FrameTile, every
+        src a contiguous fp32 (N,3,H,W) tensor on this context's device with the same N; they lie inside out and do not overlap.  rounding: "nearest"
+        (rint of s * 255, ties to even: img_as_ubyte) or "floor" (trunc: astype(np.uint8)), both clamped to [0,255].  out: a contiguous uint8 (N,Hd,Wd,3)
+        tensor to write into -- bytes no tile covers are left as they are --, else a fresh one that just holds the tiles, zero where no tile lies.
+        Inference only; no torch form (see frames_from_u8)."""
+        if self.record:
+            raise RuntimeError("Ctx.frames_to_u8: the byte conversion has no backward, not legal in a recording (training) program")
+        if rounding not in hip.U8_ROUNDINGS:
+            raise ValueError(f"frames_to_u8: rounding must be \"nearest\" or \"floor\", not {rounding!r}")
+        tiles = list(tiles)
+        if not 1 <= len(tiles) <= hip.U8_MAX_TILES:
+            raise ValueError(f"frames_to_u8: one call takes 1 to {hip.U8_MAX_TILES} tiles, not {len(tiles)}")
+        if not all(isinstance(t, FrameTile) for t in tiles):
+            raise ValueError(f"frames_to_u8: tiles are engine.FrameTile, not {[type(t).__name__ for t in tiles]}")
+        dev = torch.device(self.dev)
+        N = tiles[0].src.shape[0] if torch.is_tensor(tiles[0].src) and tiles[0].src.dim() == 4 else -1
+        desc, keep = (hip.U8Tile * len(tiles))(), []
+        for i, t in enumerate(tiles):
+            s = t.src
+            if not torch.is_tensor(s) or s.dtype != torch.float32 or s.dim() != 4 or s.shape[1] != 3 or not s.is_contiguous() or s.device != dev \
+                    or s.shape[0] != N or min(s.shape) < 1:
+                raise ValueError(f"frames_to_u8: tile {i}: src is a contiguous fp32 ({max(N, 1)},3,H,W) tensor on {self.dev}, not {self._what(s)}")
+            H, W = s.shape[2], s.shape[3]
+            if not (isinstance(t.y0, int) and isinstance(t.x0, int) and t.y0 >= 0 and t.x0 >= 0):
+                raise ValueError(f"frames_to_u8: tile {i}: y0 and x0 are integers >= 0, not {t.y0!r} and {t.x0!r}")
+            d = desc[i]
+            d.src, d.H, d.W, d.y0, d.x0, d.border = s.data_ptr(), H, W, t.y0, t.x0, int(bool(t.border))
+            if t.kp is not None:
+                kp = t.kp
+                if not torch.is_tensor(kp) or kp.dim() != 3 or kp.shape[0] != N or kp.shape[2] != 2 or kp.device != dev:
+                    raise ValueError(f"frames_to_u8: tile {i}: kp is an ({N},K,2) tensor on {self.dev}, not {self._what(kp)}")
+                K = kp.shape[1]
+                if not 1 <= K <= hip.U8_MAX_KP:
+                    raise ValueError(f"frames_to_u8: tile {i}: 1 <= K <= {hip.U8_MAX_KP} keypoints (K {K})")
+                col = t.colors
+                if not torch.is_tensor(col) or tuple(col.shape) != (K, 3) or col.device != dev:
+                    raise ValueError(f"frames_to_u8: tile {i}: keypoints need colors, a ({K},3) tensor on {self.dev}, not {self._what(col)}")
+                radius = float(t.radius)
+                if not (radius > 0 and radius != float("inf")):
+                    raise ValueError(f"frames_to_u8: tile {i}: the radius of the discs must be finite and > 0, not {t.radius!r}")
+                kp, col = self._aligned(self._cf(kp), 4), self._aligned(self._cf(col), 4)
+                keep += [kp, col]                     # alive until the launch is issued (stream order does the rest, as for every torch temporary)
+                d.kp, d.K, d.radius, d.colors = kp.data_ptr(), K, radius, col.data_ptr()
+        for i, t in enumerate(tiles):
+            for j, u in enumerate(tiles[:i]):
+                if not (t.y0 >= u.y0 + desc[j].H or u.y0 >= t.y0 + desc[i].H or t.x0 >= u.x0 + desc[j].W or u.x0 >= t.x0 + desc[i].W):
+                    raise ValueError(f"frames_to_u8: tiles {j} ({desc[j].H} x {desc[j].W} at y0 {u.y0}, x0 {u.x0}) and {i} ({desc[i].H} x {desc[i].W} at "
+                                     f"y0 {t.y0}, x0 {t.x0}) overlap")
+        Hn, Wn = max(d.y0 + d.H for d in desc), max(d.x0 + d.W for d in desc)
+        if out is None:
+            covered = sum(d.H * d.W for d in desc) == Hn * Wn
+            out = (torch.empty if covered else torch.zeros)((N, Hn, Wn, 3), dtype=torch.uint8, device=dev)
+        elif not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.dim() == 4 and out.shape[0] == N and out.shape[3] == 3 and out.is_contiguous()
+                  and out.device == dev):
+            raise ValueError(f"frames_to_u8: out is a contiguous uint8 ({N},Hd,Wd,3) tensor on {self.dev}, not {self._what(out)}")
+        Hd, Wd = out.shape[1], out.shape[2]
+        if Hn > Hd or Wn > Wd:
+            raise ValueError(f"frames_to_u8: the tiles reach row {Hn} and column {Wn}, outside out ({Hd} x {Wd})")
+        self._need_frames_entry("mrfa_frames_to_u8")
+        self._chk(self.L.mrfa_frames_to_u8(self.s, desc, len(tiles), N, out.data_ptr(), Hd, Wd, hip.U8_ROUNDINGS[rounding]), "frames_to_u8")
         return out
 
     @staticmethod

@@ -112,6 +112,12 @@ class BnBwdParams(C.Structure):
     ]
 
 
+class U8Tile(C.Structure):
+    """mrfa_u8_tile of include/mrfa_hip_ext.h: one tile of mrfa_frames_to_u8"""
+    _fields_ = [("src", C.c_void_p), ("H", C.c_int), ("W", C.c_int), ("y0", C.c_int), ("x0", C.c_int), ("kp", C.c_void_p), ("K", C.c_int),
+                ("radius", C.c_float), ("colors", C.c_void_p), ("border", C.c_int)]
+
+
 class PriorParams(C.Structure):
     _fields_ = [
         ("kd", C.c_void_p), ("ks", C.c_void_p), ("jd", C.c_void_p), ("js", C.c_void_p), ("bg", C.c_void_p),
@@ -231,7 +237,11 @@ _EXT_SIGNATURES = {
     "mrfa_kp_pose_dist": ([_V, _V, _V, _I, _I, _I, _V, _V, _V], C.c_int),
     "mrfa_frame_metrics_workspace": ([_I, _I, _I, _I], C.c_longlong),
     "mrfa_frame_metrics": ([_V, _V, _V, _I, _I, _I, _I, _I, _V, _L, _V], C.c_int),
+    "mrfa_frames_from_u8": ([_V, _V, _I, _I, _I, _I, _V], C.c_int),
+    "mrfa_frames_to_u8": ([_V, C.POINTER(U8Tile), _I, _I, _V, _I, _I, _I], C.c_int),
 }
+U8_MAX_TILES, U8_MAX_KP = 8, 64      # MRFA_U8_MAX_TILES, MRFA_U8_MAX_KP
+U8_ROUNDINGS = {"nearest": 0, "floor": 1}
 LN_SLOTS = 16          # MRFA_LN_SLOTS
 RESIZE_SUM_TERMS = 4   # MRFA_RESIZE_SUM_TERMS
 ABI_VERSION = 11       # MRFA_ABI_VERSION of include/mrfa_hip.h: the struct layouts above mirror THAT header; lib() refuses any other library
