@@ -1,4 +1,4 @@
-"""What the per-element kernel tests share (tests/test_sample_kernels_gpu.py, tests/test_token_kernels_gpu.py): operands inside wider buffers whose surroundings are
+"""What the per-element kernel tests share (tests/test_sample_kernels_gpu.py, tests/test_token_kernels_gpu.py, tests/test_norm_kernels_gpu.py): operands inside wider buffers whose surroundings are
 watched, the |got - ref| <= bound assertion, and the err / bound ratios each test prints."""
 import torch
 
@@ -10,13 +10,14 @@ F64 = torch.float64
 
 
 class Buf:
-    """values [rows, C] inside a [lead + groups * gstride] float buffer filled with `fill`: row r of group j starts at lead + j * gstride + r * ld"""
+    """values [rows, C] inside a [lead + groups * gstride] buffer of `dtype` (float32; float64 for the BatchNorm statistics blocks) filled with `fill`: row r of
+    group j starts at lead + j * gstride + r * ld"""
 
-    def __init__(self, vals, groups, ld, fill, lead=0, gap=0, dev=DEV):
+    def __init__(self, vals, groups, ld, fill, lead=0, gap=0, dev=DEV, dtype=torch.float32):
         rows_all, Cc = vals.shape
         self.rows, self.C, self.ld, self.groups, self.lead = rows_all // groups, Cc, ld, groups, lead
         self.gstride = self.rows * ld + gap
-        self.flat = torch.full((lead + groups * self.gstride,), fill, dtype=torch.float32)
+        self.flat = torch.full((lead + groups * self.gstride,), fill, dtype=dtype)
         self.fill = fill
         self._view(self.flat)[..., :Cc] = vals.view(groups, self.rows, Cc)
         self.orig = self.flat.clone()
@@ -27,7 +28,7 @@ class Buf:
 
     @property
     def ptr(self):
-        return self.flat.data_ptr() + 4 * self.lead
+        return self.flat.data_ptr() + self.flat.element_size() * self.lead
 
     def _sync(self):
         if self.flat.is_cuda:

@@ -1039,7 +1039,7 @@ def test_pack_modes(mode):
 @pytest.mark.parametrize("Cc,ld,N", [(96, 100, 2), (37, 41, 2), (132, 132, 5)])
 def test_bn_forward_backward(Cc, ld, N):
     """(96, 100) and (132, 132): float4 backward kernels (132 = 2 channel blocks + a 4-channel tail, 5*8*6 rows = ragged
-    row blocks); (37, 41): scalar kernels"""
+    row blocks); (37, 41): scalar kernels.  Per-element coverage of every dispatch path against float64: tests/test_norm_kernels_gpu.py"""
     def run(side):
         H, W = 8, 6
         x = side.t("bn/x", (N * H * W, ld), -2, 2)
@@ -1477,7 +1477,7 @@ def test_bn_statistic_groups(Cc, ld, N, G, res):
     """v7, statistic groups: mrfa_bn_finalize_groups + mrfa_bn_act_fwd / mrfa_bn_act_bwd with groups = G on a batch of G x (N / G) samples
     (1) against the CPU specification and (2) against G UNGROUPED calls of the same entry points on the G sample ranges -- outputs, dx, the
     residual gradient, running statistics after G momentum updates in group order, gamma / beta gradients summed over the groups.
-    (32 / 64 / 132 channels: float4 kernels; 37: scalar kernels.)"""
+    (32 / 64 / 132 channels: float4 kernels; 37: scalar kernels.)  Per-element coverage, with pool and blend, against float64: tests/test_norm_kernels_gpu.py"""
     H, W = 8, 8
     rows, n = N * H * W, N // G
 
@@ -1549,7 +1549,8 @@ def test_bn_statistic_groups(Cc, ld, N, G, res):
 # ---------------------------------------------------------------------------------------------- K21 (MTIA prior)
 @pytest.mark.parametrize("Cc,ld", [(64, 64), (37, 41)])
 def test_bn_residual(Cc, ld):
-    """y = relu(bn(x) + res) and its backward incl. the residual gradient (float4 and scalar kernels)"""
+    """y = relu(bn(x) + res) and its backward incl. the residual gradient (float4 and scalar kernels).  Per-element coverage against float64:
+    tests/test_norm_kernels_gpu.py"""
     def run(side):
         N, H, W = 2, 8, 6
         rows = N * H * W
