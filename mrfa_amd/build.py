@@ -27,7 +27,7 @@ def _stale(out, deps):
 def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(LIBDIR, exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    headers = [os.path.join(ROOT, "include", h) for h in ("mrfa_hip.h", "mrfa_hip_ext.h")] + sorted(glob.glob(os.path.join(CSRC, "*.h")))
+    headers = [os.path.join(ROOT, "include", "mrfa_hip.h")] + sorted(glob.glob(os.path.join(CSRC, "*.h")))
     objs = []
     procs = []
     for src in SOURCES:

@@ -1,6 +1,6 @@
 // frames: the two ends of an inference loop as the reference's callers hold them -- uint8 H x W x C frames in (frames_dataset.py:29-65) and uint8
 // H x W x 3 frames or a composed grid out (demo.py:72,160; reconstruction.py:63-76; logger.py:91-152) -- against the planar fp32 (N,3,H,W) in [0,1] that
-// every entry of infer.py takes and returns.  Entries and their rules: include/mrfa_hip_ext.h (that comment is the specification).  Inference only.
+// every entry of infer.py takes and returns.  Entries and their rules: include/mrfa_hip.h (that comment is the specification).  Inference only.
 //
 // Both kernels are pure data movement: one thread owns FOUR consecutive pixels of one row, which are 16 bytes in each fp32 plane and 4 Cin / 12 bytes on the
 // byte side.  No LDS (nothing is read twice), no atomics, no scratch; every output byte has one writer: two runs are bit-identical.
@@ -20,7 +20,7 @@
 #include <math.h>
 
 #include "common.h"
-#include "mrfa_hip_ext.h"
+#include "mrfa_hip.h"
 
 namespace {
 

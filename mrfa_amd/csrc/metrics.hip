@@ -1,6 +1,6 @@
 // frame_metrics: the full-reference metrics of a clip -- mean |p - t|, mean (p - t)^2 and SSIM of frame n of `pred` against frame n of `target` -- in one
 // entry per group of frames, the rows kept on the device (reconstruction.py:52-70 prints L1 and PSNR per frame and declares an SSIM list it never fills).
-// Entry: include/mrfa_hip_ext.h.  Inference only.
+// Entry: include/mrfa_hip.h.  Inference only.
 //
 // SSIM (Wang et al. 2004, data range 1): an 11-tap separable Gaussian window (sigma 1.5; the eleven fp32 numbers below ARE the definition), "valid"
 // (no padding: (H - 10) x (W - 10) windows per channel), the five moments mu_x, mu_y, E[x^2], E[y^2], E[xy], no clamping of the variances,
@@ -23,7 +23,7 @@
 #include <limits.h>
 
 #include "common.h"
-#include "mrfa_hip_ext.h"
+#include "mrfa_hip.h"
 
 namespace {
 

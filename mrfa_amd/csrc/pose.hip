@@ -1,5 +1,5 @@
 // kp_pose_dist: the pose distance of driving frames to their source from the model's keypoints, with a running argmin over a clip kept on the device
-// (demo.py:75-98, find_best_frame, with the 68 face landmarks replaced by the K keypoints).  Entry: include/mrfa_hip_ext.h.  Inference only.
+// (demo.py:75-98, find_best_frame, with the 68 face landmarks replaced by the K keypoints).  Entry: include/mrfa_hip.h.  Inference only.
 //
 // One workgroup of ONE wave per source; lane l takes frames l, l + 64, ... of that source, one whole frame per lane: K <= 64 points are a few hundred
 // operations, the point of the kernel is that a clip's search is one launch per group of frames and one host read at its end.  Per frame, in this order
@@ -14,7 +14,7 @@
 #include <limits.h>
 
 #include "common.h"
-#include "mrfa_hip_ext.h"
+#include "mrfa_hip.h"
 
 namespace {
 

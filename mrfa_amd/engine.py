@@ -308,13 +308,13 @@ BRANCH_STREAMS = os.environ.get("MRFA_BRANCH_STREAMS", "1") != "0"        # (kep
 # (batch statistics, scale / shift, the backward's sums; `groups` momentum updates of the running statistics in group order; num_batches_tracked += groups);
 # everything else has no cross-sample coupling.  Half / a third of the launches of a latency-bound chain, twice / three times the rows per launch.
 STAT_GROUPS = 1
-# (TH, TW) of mrfa_frame_metrics (MRFA_METRICS_TILE_H / _W of include/mrfa_hip_ext.h): one workgroup per tile, channel and frame; a tile owns the SSIM windows
+# (TH, TW) of mrfa_frame_metrics (MRFA_METRICS_TILE_H / _W of include/mrfa_hip.h): one workgroup per tile, channel and frame; a tile owns the SSIM windows
 # whose top-left corner lies in it.  Exported for the tests, which place their shapes on the seams, and for the specification's workspace size
 METRICS_TILE = (32, 32)
 
 
 class FrameTile(NamedTuple):
-    """one tile of Ctx.frames_to_u8 (mrfa_u8_tile of include/mrfa_hip_ext.h): image n of src (N,3,H,W) fp32 goes to dst[n, y0:y0+H, x0:x0+W, :]; kp (N,K,2)
+    """one tile of Ctx.frames_to_u8 (mrfa_u8_tile of include/mrfa_hip.h): image n of src (N,3,H,W) fp32 goes to dst[n, y0:y0+H, x0:x0+W, :]; kp (N,K,2)
     with colors (K,3) draws discs of `radius` pixels, border sets the tile's first and last column to 255"""
     src: torch.Tensor
     y0: int = 0
@@ -1822,9 +1822,7 @@ class Ctx:
         """(kd - k0) * scale + ks and jd inv(j0) js of normalize_kp (animate_ddp.py:17-37) in one launch: kd / jd (B,K,2) / (B,K,2,2) of the driving frames,
         k0 / j0 and ks / js of the B / rep first driving frames and sources (frame n reads entry n // rep).  scale: a one-element fp32 DEVICE tensor (the
         kernel reads it) or None for 1.  -> (kp, jacobian or None), fresh tensors.  The kernel loads float2 / float4: an operand that is a view at an
-        offset which is not 8-byte (keypoints) / 16-byte (Jacobians) aligned is copied first.  Inference only: the kernel has no backward.
-        A version-11 library built before mrfa_kp_relative_fwd existed (the entry is additive: hip.ADDITIVE_SYMBOLS) has no such kernel; then, with ONE
-        RuntimeWarning per process, the same arithmetic runs as torch operations (normalize_kp's launches, on expanded views of k0 / ks)."""
+        offset which is not 8-byte (keypoints) / 16-byte (Jacobians) aligned is copied first.  Inference only: the kernel has no backward."""
         if self.record:
             raise RuntimeError("Ctx.kp_relative: the relative keypoints have no backward, not legal in a recording (training) program")
         jacs = (jd, j0, js)
@@ -1836,8 +1834,6 @@ class Ctx:
             f"kp_relative: entry n // rep for frame n ({B} frames, {k0.shape[0]} initial frames, {ks.shape[0]} sources, rep {rep})"
         if scale is not None:
             assert scale.dtype == torch.float32 and scale.numel() == 1 and scale.device == kd.device, "kp_relative: scale is one fp32 element on the keypoints' device"
-        if not hip.has("mrfa_kp_relative_fwd"):
-            return self._kp_relative_older_library(kd, k0, ks, jd, j0, js, scale, rep)
         kp_out = torch.empty_like(kd)
         jac_out = torch.empty_like(jd) if jd is not None else None
         p = lambda t: None if t is None else t.data_ptr()
@@ -1846,10 +1842,9 @@ class Ctx:
 
     def kp_pose_dist(self, kd, ks, rep: int = 1, state: Optional[torch.Tensor] = None, want_dist: bool = True, want_area: bool = False):
         """Pose distance of B = Bs rep driving frames kd (B,K,2) to their sources ks (Bs,K,2), frame n against source n // rep, in one launch
-        (mrfa_kp_pose_dist, include/mrfa_hip_ext.h): centre the keypoints, divide by the square root of their convex-hull area, sum the squared differences
+        (mrfa_kp_pose_dist, include/mrfa_hip.h): centre the keypoints, divide by the square root of their convex-hull area, sum the squared differences
         (demo.py:75-98 on keypoints).  state: None or infer.pose_state(Bs, device), the running argmin of a clip, updated IN PLACE on the device (frame j of
-        this call has clip index frames_seen + j).  -> (dist (B) or None, hull area (B) or None), fresh tensors.  Inference only; 3 <= K <= 64.
-        The entry is not part of include/mrfa_hip.h's table: a library built before it existed has no such kernel, and there is no torch form."""
+        this call has clip index frames_seen + j).  -> (dist (B) or None, hull area (B) or None), fresh tensors.  Inference only; 3 <= K <= 64."""
         if self.record:
             raise RuntimeError("Ctx.kp_pose_dist: the pose distance has no backward, not legal in a recording (training) program")
         kd, ks = (self._aligned(self._cf(t), 8) for t in (kd, ks))
@@ -1865,9 +1860,6 @@ class Ctx:
         if state is not None and not (state.dtype == torch.int32 and tuple(state.shape) == (B // rep, 4) and state.is_contiguous() and state.device == kd.device):
             raise ValueError(f"kp_pose_dist: state is a contiguous int32 ({B // rep},4) tensor on the keypoints' device (infer.pose_state), not "
                              f"{state.dtype} {tuple(state.shape)} on {state.device}")
-        if not hip.has("mrfa_kp_pose_dist"):
-            raise RuntimeError(f"the loaded version-{hip.ABI_VERSION} library has no mrfa_kp_pose_dist (it was built before the entry was added, "
-                               "include/mrfa_hip_ext.h) and the pose distance has no other form: rebuild it with `python -m mrfa_amd.build --force`")
         dist = torch.empty(B, dtype=torch.float32, device=kd.device) if want_dist else None
         area = torch.empty(B, dtype=torch.float32, device=kd.device) if want_area else None
         p = lambda t: None if t is None else t.data_ptr()
@@ -1877,11 +1869,10 @@ class Ctx:
     _metrics_ws: dict = {}                             # (device, stream, N, C, H, W) -> workspace of mrfa_frame_metrics, one per shape seen
 
     def frame_metrics(self, pred: torch.Tensor, target: torch.Tensor, want_ssim: bool = True) -> torch.Tensor:
-        """L1, MSE and SSIM of frame n of pred (N,C,H,W) against frame n of target in one entry call (mrfa_frame_metrics, include/mrfa_hip_ext.h: two
+        """L1, MSE and SSIM of frame n of pred (N,C,H,W) against frame n of target in one entry call (mrfa_frame_metrics, include/mrfa_hip.h: two
         launches on this stream, nothing waits for the host) -> a fresh (N,4) fp32 tensor on the frames' device, rows {l1, mse, ssim, 0}; ssim is 0 with
         want_ssim=False and needs min(H, W) >= 11 otherwise.  Both operands contiguous fp32 on one device: nothing is copied or converted here.
-        Inference only.  The entry is not part of include/mrfa_hip.h's table: a library built before it existed has no such kernel, and there is no torch
-        form."""
+        Inference only."""
         if self.record:
             raise RuntimeError("Ctx.frame_metrics: the frame metrics have no backward, not legal in a recording (training) program")
         for name, t in (("pred", pred), ("target", target)):
@@ -1896,9 +1887,6 @@ class Ctx:
             raise ValueError(f"frame_metrics: N, C, H and W must be >= 1, not {tuple(pred.shape)}")
         if want_ssim and min(H, W) < 11:
             raise ValueError(f"frame_metrics: SSIM needs one 11 x 11 window, min(H, W) >= 11 ({H} x {W}); want_ssim=False gives L1 and MSE alone")
-        if not (hip.has("mrfa_frame_metrics") and hip.has("mrfa_frame_metrics_workspace")):
-            raise RuntimeError(f"the loaded version-{hip.ABI_VERSION} library has no mrfa_frame_metrics (it was built before the entry was added, "
-                               "include/mrfa_hip_ext.h) and the frame metrics have no other form: rebuild it with `python -m mrfa_amd.build --force`")
         key = (pred.device, self.s, N, C, H, W)
         ws = Ctx._metrics_ws.get(key)
         if ws is None:
@@ -1915,16 +1903,10 @@ class Ctx:
     def _what(t) -> str:
         return f"{t.dtype} {tuple(t.shape)} {'contiguous' if t.is_contiguous() else 'strided'} on {t.device}" if torch.is_tensor(t) else type(t).__name__
 
-    def _need_frames_entry(self, name: str):
-        if not hip.has(name):
-            raise RuntimeError(f"the loaded version-{hip.ABI_VERSION} library has no {name} (it was built before the entry was added, "
-                               "include/mrfa_hip_ext.h) and the byte frames have no other form: rebuild it with `python -m mrfa_amd.build --force`")
-
     def frames_from_u8(self, u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """uint8 frames (N,H,W,Cin), Cin in {1,3,4}, contiguous on this context's device -> fp32 (N,3,H,W) = byte * fl32(1/255) in one launch
-        (mrfa_frames_from_u8, include/mrfa_hip_ext.h): grey goes to all three planes, alpha is dropped.  out: a contiguous fp32 (N,3,H,W) tensor on the
-        same device to write into (a captured program's static input), else a fresh one.  Inference only.  The entry is not part of include/mrfa_hip.h's
-        table: a library built before it existed has no such kernel, and there is no torch form."""
+        (mrfa_frames_from_u8, include/mrfa_hip.h): grey goes to all three planes, alpha is dropped.  out: a contiguous fp32 (N,3,H,W) tensor on the
+        same device to write into (a captured program's static input), else a fresh one.  Inference only."""
         if self.record:
             raise RuntimeError("Ctx.frames_from_u8: the byte conversion has no backward, not legal in a recording (training) program")
         if not torch.is_tensor(u8) or u8.dtype != torch.uint8 or u8.dim() != 4 or not u8.is_contiguous() or u8.device != torch.device(self.dev):
@@ -1936,16 +1918,15 @@ class Ctx:
             out = torch.empty((N, 3, H, W), dtype=torch.float32, device=u8.device)
         elif not (torch.is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == (N, 3, H, W) and out.is_contiguous() and out.device == u8.device):
             raise ValueError(f"frames_from_u8: out is a contiguous fp32 {(N, 3, H, W)} tensor on {u8.device}, not {self._what(out)}")
-        self._need_frames_entry("mrfa_frames_from_u8")
         self._chk(self.L.mrfa_frames_from_u8(self.s, u8.data_ptr(), N, H, W, Cin, out.data_ptr()), "frames_from_u8")
         return out
 
     def frames_to_u8(self, tiles: Sequence[FrameTile], out: Optional[torch.Tensor] = None, rounding: str = "nearest") -> torch.Tensor:
-        """fp32 frames -> uint8 (N,Hd,Wd,3) in one launch (mrfa_frames_to_u8, include/mrfa_hip_ext.h).  tiles: 1..8 FrameTile, every
+        """fp32 frames -> uint8 (N,Hd,Wd,3) in one launch (mrfa_frames_to_u8, include/mrfa_hip.h).  tiles: 1..8 FrameTile, every
         src a contiguous fp32 (N,3,H,W) tensor on this context's device with the same N; they lie inside out and do not overlap.  rounding: "nearest"
         (rint of s * 255, ties to even: img_as_ubyte) or "floor" (trunc: astype(np.uint8)), both clamped to [0,255].  out: a contiguous uint8 (N,Hd,Wd,3)
         tensor to write into -- bytes no tile covers are left as they are --, else a fresh one that just holds the tiles, zero where no tile lies.
-        Inference only; no torch form (see frames_from_u8)."""
+        Inference only."""
         if self.record:
             raise RuntimeError("Ctx.frames_to_u8: the byte conversion has no backward, not legal in a recording (training) program")
         if rounding not in hip.U8_ROUNDINGS:
@@ -1999,32 +1980,12 @@ class Ctx:
         Hd, Wd = out.shape[1], out.shape[2]
         if Hn > Hd or Wn > Wd:
             raise ValueError(f"frames_to_u8: the tiles reach row {Hn} and column {Wn}, outside out ({Hd} x {Wd})")
-        self._need_frames_entry("mrfa_frames_to_u8")
         self._chk(self.L.mrfa_frames_to_u8(self.s, desc, len(tiles), N, out.data_ptr(), Hd, Wd, hip.U8_ROUNDINGS[rounding]), "frames_to_u8")
         return out
 
     @staticmethod
     def _aligned(t: Optional[torch.Tensor], nbytes: int) -> Optional[torch.Tensor]:
         return t if t is None or t.data_ptr() % nbytes == 0 else t.clone()
-
-    _warned_no_kp_relative = False
-
-    @staticmethod
-    def _kp_relative_older_library(kd, k0, ks, jd, j0, js, scale, rep):
-        if not Ctx._warned_no_kp_relative:
-            Ctx._warned_no_kp_relative = True
-            import warnings
-            warnings.warn(f"the loaded version-{hip.ABI_VERSION} library has no mrfa_kp_relative_fwd (it was built before the entry was added): the relative "
-                          "keypoints run as torch operations, about twenty small launches per call.  Rebuild it with `python -m mrfa_amd.build --force`",
-                          RuntimeWarning, stacklevel=3)
-        rf = lambda t: t if rep == 1 else t.unsqueeze(1).expand(t.shape[0], rep, *t.shape[1:]).reshape(t.shape[0] * rep, *t.shape[1:])
-        kp = (kd - rf(k0)) * (scale if scale is not None else 1) + rf(ks)
-        if jd is None:
-            return kp, None
-        z = rf(j0)
-        a, b, c, d = z[..., 0, 0], z[..., 0, 1], z[..., 1, 0], z[..., 1, 1]
-        inv = torch.stack([torch.stack([d, -b], dim=-1), torch.stack([-c, a], dim=-1)], dim=-2) / (a * d - b * c)[..., None, None]
-        return kp, torch.matmul(torch.matmul(jd, inv), rf(js))
 
     def prior_motion(self, src: View, kd, ks, jd, js, bg, variance: float):
         """DenseMotionNetwork's heat-map differences, sparse motions and the K+1 warps of the 1/4-scale source in one launch

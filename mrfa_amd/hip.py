@@ -113,7 +113,7 @@ class BnBwdParams(C.Structure):
 
 
 class U8Tile(C.Structure):
-    """mrfa_u8_tile of include/mrfa_hip_ext.h: one tile of mrfa_frames_to_u8"""
+    """mrfa_u8_tile of include/mrfa_hip.h: one tile of mrfa_frames_to_u8"""
     _fields_ = [("src", C.c_void_p), ("H", C.c_int), ("W", C.c_int), ("y0", C.c_int), ("x0", C.c_int), ("kp", C.c_void_p), ("K", C.c_int),
                 ("radius", C.c_float), ("colors", C.c_void_p), ("border", C.c_int)]
 
@@ -225,26 +225,19 @@ _SIGNATURES = {
     "mrfa_adam_prepare": ([_V, _V, _I, C.c_double, C.c_double], C.c_int),
     "mrfa_grad_absmax": ([_V, _V, _L, _V, _I], C.c_int),
     "mrfa_adam_flat": ([_V, _V, _V, _V, _V, _L, _V, C.c_double, C.c_double, _F, _F, _I, _F], C.c_int),
-}
-
-EXPORTED_SYMBOLS = tuple(_SIGNATURES)
-# entries added to ABI version 11 without moving the number (include/mrfa_hip.h): a version-11 library built before one of them lacks it.  lib() loads such a
-# library; the one caller of the entry (engine.Ctx.kp_relative) looks the symbol up with has() and says what it does without it
-ADDITIVE_SYMBOLS = ("mrfa_kp_relative_fwd",)
-# entries of include/mrfa_hip_ext.h: a table of their own, outside _SIGNATURES / EXPORTED_SYMBOLS / ADDITIVE_SYMBOLS (those three mirror include/mrfa_hip.h).
-# lib() binds the ones the library exports and skips the others; the one caller of each asks has() and says that the library has to be rebuilt
-_EXT_SIGNATURES = {
     "mrfa_kp_pose_dist": ([_V, _V, _V, _I, _I, _I, _V, _V, _V], C.c_int),
     "mrfa_frame_metrics_workspace": ([_I, _I, _I, _I], C.c_longlong),
     "mrfa_frame_metrics": ([_V, _V, _V, _I, _I, _I, _I, _I, _V, _L, _V], C.c_int),
     "mrfa_frames_from_u8": ([_V, _V, _I, _I, _I, _I, _V], C.c_int),
     "mrfa_frames_to_u8": ([_V, C.POINTER(U8Tile), _I, _I, _V, _I, _I, _I], C.c_int),
 }
-U8_MAX_TILES, U8_MAX_KP = 8, 64      # MRFA_U8_MAX_TILES, MRFA_U8_MAX_KP
-U8_ROUNDINGS = {"nearest": 0, "floor": 1}
+
+EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+U8_MAX_TILES, U8_MAX_KP = 8, 64      # MRFA_U8_MAX_TILES, MRFA_U8_MAX_KP of include/mrfa_hip.h
+U8_ROUNDINGS = {"nearest": 0, "floor": 1}     # the `rounding` argument of mrfa_frames_to_u8 (include/mrfa_hip.h)
 LN_SLOTS = 16          # MRFA_LN_SLOTS
 RESIZE_SUM_TERMS = 4   # MRFA_RESIZE_SUM_TERMS
-ABI_VERSION = 11       # MRFA_ABI_VERSION of include/mrfa_hip.h: the struct layouts above mirror THAT header; lib() refuses any other library
+ABI_VERSION = 12       # MRFA_ABI_VERSION of include/mrfa_hip.h: the struct layouts above mirror THAT header; lib() refuses any other library
 # pack modes of mrfa_pack_conv_weight / mrfa_pack_conv_weights_multi: the table above mrfa_pack_conv_weight in include/mrfa_hip.h
 PACK_FWD, PACK_FWD_FLAT, PACK_DGRAD, PACK_DGRAD_FLAT = 0, 1, 2, 3        # fp32, chunked / flat-K
 PACK_FEWOUT, PACK_FEWIN = 5, 7                                           # fp32, the few-channel direct kernels
@@ -269,20 +262,14 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python -m mrfa_amd.build` (hipcc --offload-arch=gfx950). "
                 "mrfa_amd has no CPU fallback.")
         L = C.CDLL(LIB_PATH)
-        for name, (argtypes, restype) in _SIGNATURES.items():
-            fn = getattr(L, name, None) if name in ADDITIVE_SYMBOLS else getattr(L, name)          # AttributeError if the ABI and the header drift apart
-            if fn is None:
-                continue
-            fn.argtypes = argtypes
-            fn.restype = restype
-        for name, (argtypes, restype) in _EXT_SIGNATURES.items():
-            fn = getattr(L, name, None)
-            if fn is not None:
-                fn.argtypes = argtypes
-                fn.restype = restype
-        if L.mrfa_version() != ABI_VERSION:
+        L.mrfa_version.argtypes, L.mrfa_version.restype = _SIGNATURES["mrfa_version"]
+        if L.mrfa_version() != ABI_VERSION:    # first: a library of an older version lacks entries too, and this is the message that says what to do
             raise RuntimeError(f"{LIB_PATH} speaks ABI version {L.mrfa_version()}, this binding was written against {ABI_VERSION} "
                                "(include/mrfa_hip.h MRFA_ABI_VERSION): rebuild the library (`python -m mrfa_amd.build --force`)")
+        for name, (argtypes, restype) in _SIGNATURES.items():
+            fn = getattr(L, name)          # AttributeError if the ABI and the header drift apart
+            fn.argtypes = argtypes
+            fn.restype = restype
         _lib = L
         mode = os.environ.get("MRFA_MFMA", DEFAULT_MFMA)
         if mode not in MFMA_MODES:
@@ -310,11 +297,6 @@ def set_mfma_mode(mode: str):
 def mfma_mode() -> str:
     m = lib().mrfa_get_mfma_mode()
     return next(k for k, v in MFMA_MODES.items() if v == m)
-
-
-def has(name: str) -> bool:
-    """whether the loaded library exports `name` (one of ADDITIVE_SYMBOLS or _EXT_SIGNATURES; every other entry is there or lib() raised)"""
-    return getattr(lib(), name, None) is not None
 
 
 def check(rc: int, what: str):

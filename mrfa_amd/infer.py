@@ -55,7 +55,7 @@ def _check_output(output, what: str) -> str:
 @torch.no_grad()
 def frames_from_uint8(frames: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """uint8 frames (N,H,W,C) or one frame (H,W,C), C in {1,3,4}, as an image reader returns them -> fp32 (N,3,H,W) in [0,1] on the same device, one launch
-    (mrfa_frames_from_u8, include/mrfa_hip_ext.h): byte * fl32(1/255), what img_as_float32 gives; a grey frame fills all three planes and alpha is dropped
+    (mrfa_frames_from_u8, include/mrfa_hip.h): byte * fl32(1/255), what img_as_float32 gives; a grey frame fills all three planes and alpha is dropped
     (frames_dataset.py:29-65).  out: a contiguous fp32 (N,3,H,W) tensor to write into."""
     if not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() not in (3, 4):
         raise ValueError(f"frames_from_uint8: frames are a uint8 (N,H,W,C) or (H,W,C) tensor, not {_describe(frames)}")
@@ -361,7 +361,7 @@ _INF_BITS = 0x7F800000          # +inf as the int32 that shares its bits
 
 
 def pose_state(bs: int, device) -> torch.Tensor:
-    """a fresh running argmin for bs sources (mrfa_kp_pose_dist's state, include/mrfa_hip_ext.h): (bs,4) int32 rows {best distance as fp32 bits = +inf,
+    """a fresh running argmin for bs sources (mrfa_kp_pose_dist's state, include/mrfa_hip.h): (bs,4) int32 rows {best distance as fp32 bits = +inf,
     best index 0, frames seen 0, pad}.  Column 1 is the answer; a clip with no finite distance leaves it at 0, as the reference's loop does."""
     st = torch.zeros(bs, 4, dtype=torch.int32, device=device)
     st[:, 0] = _INF_BITS
@@ -478,7 +478,7 @@ def _psnr_of_mse(mse):
 
 def ssim(img1: torch.Tensor, img2: torch.Tensor) -> torch.Tensor:
     """SSIM of image n of img1 against image n of img2, both (N,C,H,W) contiguous fp32 in [0,1] on one device -> (N,) fp32 on that device: Wang et al.
-    2004 with an 11-tap Gaussian window (sigma 1.5), no padding, C1 = 0.01^2, C2 = 0.03^2, the mean over channels and windows (include/mrfa_hip_ext.h,
+    2004 with an 11-tap Gaussian window (sigma 1.5), no padding, C1 = 0.01^2, C2 = 0.03^2, the mean over channels and windows (include/mrfa_hip.h,
     mrfa_frame_metrics).  The reference declares a loss_list_ssim and never fills it (reconstruction.py:43)."""
     from .engine import Ctx
     return Ctx(img1.device, train=False, record=False).frame_metrics(img1, img2, want_ssim=True)[:, 2]

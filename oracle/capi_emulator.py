@@ -10,12 +10,19 @@ mrfa_amd never imports this file; without libmrfa_hip.so the product raises.
 from __future__ import annotations
 
 import ctypes as C
+import math
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
+from mrfa_amd.hip import U8_MAX_KP, U8_MAX_TILES, U8Tile      # the binding's mirror of mrfa_u8_tile and its limits (tests/test_frame_io_cpu.py holds them to the header)
+from oracle import infer_spec
+
 
 STATS_SLOTS = 32        # MRFA_STATS_SLOTS (include/mrfa_hip.h)
+METRICS_TILE = (32, 32)  # MRFA_METRICS_TILE_H, MRFA_METRICS_TILE_W
+POSE_MAX_K = 64         # most keypoints of mrfa_kp_pose_dist
 
 
 def _flat(ptr: int, n: int, dtype=torch.float32) -> torch.Tensor:
@@ -38,6 +45,14 @@ def bf16_mat(ptr: int, rows: int, ld: int, cols: int) -> torch.Tensor:
 def nhwc(ptr, N, H, W, ld, Cc) -> torch.Tensor:
     return mat(ptr, N * H * W, ld, Cc).view(N, H, W, Cc) if ld == Cc else \
         torch.as_strided(_flat(ptr, (N * H * W - 1) * ld + Cc), (N, H, W, Cc), (H * W * ld, W * ld, ld, 1))
+
+
+def _f32(ptr: int, n: int) -> np.ndarray:
+    return np.ctypeslib.as_array((C.c_float * n).from_address(ptr))
+
+
+def _u8(ptr: int, n: int) -> np.ndarray:
+    return np.ctypeslib.as_array((C.c_ubyte * n).from_address(ptr))
 
 
 def vec(ptr, n, dtype=torch.float32):
@@ -255,6 +270,137 @@ class Emulator:
             _flat(jac_out, B * K * 4).view(B, K, 2, 2).copy_(new["jacobian"])
         return 0
 
+    # ---------------------------------------------------------------- inference-loop entries (csrc/pose.hip, metrics.hip, frames.hip): oracle/infer_spec.py
+    def mrfa_kp_pose_dist(self, stream, kp_d, kp_s, B, rep, K, dist_out, area_out, state):
+        bad = None
+        if not (kp_d and kp_s):
+            bad = "null keypoint pointer"
+        elif not (dist_out or area_out or state):
+            bad = "dist_out, area_out and state are all null (nothing to compute)"
+        elif B < 1 or rep < 1 or K < 1:
+            bad = f"B, rep and K must be >= 1 (B {B}, rep {rep}, K {K})"
+        elif B % rep:
+            bad = f"rep must divide B (B {B}, rep {rep})"
+        elif not 3 <= K <= POSE_MAX_K:
+            bad = f"a hull needs 3 <= K <= {POSE_MAX_K} keypoints (K {K})"
+        elif kp_d % 8 or kp_s % 8 or any(p and p % 4 for p in (dist_out, area_out, state)):
+            bad = "keypoints must be 8-byte aligned (vector loads), the outputs and the state 4-byte aligned"
+        if bad:
+            self._err = ("kp_pose_dist: " + bad).encode()
+            return 1
+        Bs = B // rep
+        dist64, area64 = infer_spec.pose_dist(_f32(kp_d, B * K * 2).reshape(B, K, 2), _f32(kp_s, Bs * K * 2).reshape(Bs, K, 2), rep)
+        with np.errstate(over="ignore"):
+            dist, area = dist64.astype(np.float32), area64.astype(np.float32)                 # the one rounding
+        if dist_out:
+            _f32(dist_out, B)[:] = dist
+        if area_out:
+            _f32(area_out, B)[:] = area
+        if state:
+            best, words = _f32(state, Bs * 4).reshape(Bs, 4), np.ctypeslib.as_array((C.c_int * (Bs * 4)).from_address(state)).reshape(Bs, 4)
+            for s in range(Bs):
+                for j in range(rep):
+                    if dist[s * rep + j] < best[s, 0]:                                        # strict: ties keep the earliest, NaN and +inf never win
+                        best[s, 0] = dist[s * rep + j]
+                        words[s, 1] = words[s, 2] + j
+                words[s, 2] += rep
+        return 0
+
+    def mrfa_frame_metrics_workspace(self, N, Cc, H, W):
+        if N < 1 or Cc < 1 or H < 1 or W < 1:
+            return -1
+        TH, TW = METRICS_TILE
+        wgs = N * Cc * (-(-H // TH)) * (-(-W // TW))
+        return -1 if wgs > 2 ** 31 - 1 else wgs * 24
+
+    def mrfa_frame_metrics(self, stream, pred, target, N, Cc, H, W, want_ssim, workspace, workspace_bytes, out):
+        TAPS = infer_spec.TAPS
+        bad = None
+        if not (pred and target and workspace and out):
+            bad = "null pointer"
+        elif N < 1 or Cc < 1 or H < 1 or W < 1:
+            bad = f"N, C, H and W must be >= 1 (N {N}, C {Cc}, H {H}, W {W})"
+        elif self.mrfa_frame_metrics_workspace(N, Cc, H, W) < 0:
+            bad = "the workgroups exceed one grid"
+        elif workspace_bytes < self.mrfa_frame_metrics_workspace(N, Cc, H, W):
+            bad = f"the workspace holds {workspace_bytes} bytes, mrfa_frame_metrics_workspace asks for {self.mrfa_frame_metrics_workspace(N, Cc, H, W)}"
+        elif want_ssim and min(H, W) < TAPS:
+            bad = f"SSIM needs one {TAPS} x {TAPS} window, min(H, W) >= {TAPS} (H {H}, W {W})"
+        elif pred % 4 or target % 4 or out % 4 or workspace % 8:
+            bad = "pred, target and out must be 4-byte aligned (scalar fp32 accesses), the workspace 8-byte aligned (doubles)"
+        if bad:
+            self._err = ("frame_metrics: " + bad).encode()
+            return 1
+        n = N * Cc * H * W
+        rows = infer_spec.frame_metrics(_f32(pred, n).reshape(N, Cc, H, W), _f32(target, n).reshape(N, Cc, H, W), bool(want_ssim))
+        with np.errstate(over="ignore"):
+            _f32(out, N * 4)[:] = rows.astype(np.float32).reshape(-1)                              # the one rounding
+        return 0
+
+    def mrfa_frames_from_u8(self, stream, src, N, H, W, Cin, dst):
+        bad = None
+        if not (src and dst):
+            bad = "null pointer"
+        elif N < 1 or H < 1 or W < 1:
+            bad = f"N, H and W must be >= 1 (N {N}, H {H}, W {W})"
+        elif Cin not in (1, 3, 4):
+            bad = f"Cin must be 1 (grey), 3 or 4 (alpha is dropped), not {Cin}"
+        elif dst % 4:
+            bad = "dst must be 4-byte aligned (fp32 stores)"
+        if bad:
+            self._err = ("frames_from_u8: " + bad).encode()
+            return 1
+        _f32(dst, N * 3 * H * W)[:] = infer_spec.from_u8(_u8(src, N * H * W * Cin).reshape(N, H, W, Cin)).reshape(-1)
+        return 0
+
+    def mrfa_frames_to_u8(self, stream, tiles, n_tiles, N, dst, Hd, Wd, rounding):
+        bad = None
+        if not (tiles and dst):
+            bad = "null pointer"
+        elif not 1 <= n_tiles <= U8_MAX_TILES:
+            bad = f"1 <= n_tiles <= {U8_MAX_TILES} (n_tiles {n_tiles})"
+        elif N < 1 or Hd < 1 or Wd < 1:
+            bad = f"N, Hd and Wd must be >= 1 (N {N}, Hd {Hd}, Wd {Wd})"
+        elif rounding not in (0, 1):
+            bad = f"rounding must be 0 (nearest, ties to even) or 1 (floor), not {rounding}"
+        ts = []
+        if not bad:
+            arr = C.cast(tiles, C.POINTER(U8Tile))
+            ts = [arr[i] for i in range(n_tiles)]
+        for i, t in enumerate(ts):
+            if bad:
+                break
+            if not t.src:
+                bad = f"tile {i} has a null src"
+            elif t.src % 4:
+                bad = f"tile {i}: src must be 4-byte aligned"
+            elif t.H < 1 or t.W < 1:
+                bad = f"tile {i}: H and W must be >= 1 (H {t.H}, W {t.W})"
+            elif t.y0 < 0 or t.x0 < 0 or t.y0 + t.H > Hd or t.x0 + t.W > Wd:
+                bad = f"tile {i} ({t.H} x {t.W} at y0 {t.y0}, x0 {t.x0}) lies outside dst ({Hd} x {Wd})"
+            elif t.kp and not t.colors:
+                bad = f"tile {i} has keypoints and colors == NULL"
+            elif t.kp and not 1 <= t.K <= U8_MAX_KP:
+                bad = f"tile {i}: 1 <= K <= {U8_MAX_KP} (K {t.K})"
+            elif t.kp and not (math.isfinite(t.radius) and t.radius > 0):
+                bad = f"tile {i}: the radius must be finite and > 0 (radius {t.radius:g})"
+            elif t.kp and (t.kp % 4 or t.colors % 4):
+                bad = f"tile {i}: kp and colors must be 4-byte aligned"
+            else:
+                for j, u in enumerate(ts[:i]):
+                    if not (t.y0 >= u.y0 + u.H or u.y0 >= t.y0 + t.H or t.x0 >= u.x0 + u.W or u.x0 >= t.x0 + t.W):
+                        bad = f"tiles {j} ({u.H} x {u.W} at y0 {u.y0}, x0 {u.x0}) and {i} ({t.H} x {t.W} at y0 {t.y0}, x0 {t.x0}) overlap"
+        if bad:
+            self._err = ("frames_to_u8: " + bad).encode()
+            return 1
+        out = _u8(dst, N * Hd * Wd * 3).reshape(N, Hd, Wd, 3)
+        for t in ts:
+            src = _f32(t.src, N * 3 * t.H * t.W).reshape(N, 3, t.H, t.W)
+            kp = _f32(t.kp, N * t.K * 2).reshape(N, t.K, 2) if t.kp else None
+            colors = _f32(t.colors, t.K * 3).reshape(t.K, 3) if t.kp else None
+            out[:, t.y0:t.y0 + t.H, t.x0:t.x0 + t.W, :] = infer_spec.compose_tile(src, kp, t.radius, colors, t.border, rounding)
+        return 0
+
     # ---------------------------------------------------------------- K22: training losses
     def mrfa_maxpool2_fwd(self, stream, x, ldx, N, H, W, Cc, y, ldy):
         v = F.max_pool2d(nhwc(x, N, H, W, ldx, Cc).permute(0, 3, 1, 2), 2)
@@ -399,7 +545,7 @@ class Emulator:
 
     # ---------------------------------------------------------------- misc
     def mrfa_version(self):
-        return 11             # MRFA_ABI_VERSION of include/mrfa_hip.h (tests/test_emulator_abi_cpu.py holds the three numbers together)
+        return 12             # MRFA_ABI_VERSION of include/mrfa_hip.h (tests/test_emulator_abi_cpu.py holds the three numbers together)
 
     def mrfa_last_error(self):
         return self._err

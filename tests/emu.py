@@ -24,24 +24,11 @@ class Counting:
         return call
 
 
-class _Without:
-    """a library built before the entries `names` were added: it does not have them (hip.ADDITIVE_SYMBOLS)"""
-
-    def __init__(self, emu, names):
-        self._emu, self._names = emu, names
-
-    def __getattr__(self, name):
-        if name in self._names:
-            raise AttributeError(name)
-        return getattr(self._emu, name)
-
-
 @contextlib.contextmanager
-def emulated_hip(counting=False, without=()):
-    """installs the emulator as the loaded library and yields it; counting: behind Counting; without: these entry points absent"""
+def emulated_hip(counting=False):
+    """installs the emulator as the loaded library and yields it; counting: behind Counting"""
     old_lib, old_stream = hip._lib, hip.stream_ptr
-    lib = _Without(Emulator(), tuple(without)) if without else Emulator()
-    hip._lib = Counting(lib) if counting else lib
+    hip._lib = Counting(Emulator()) if counting else Emulator()
     hip.stream_ptr = lambda: 0
     try:
         yield hip._lib

@@ -1,6 +1,6 @@
-"""The best driving frame from the model's keypoints, on the CPU through the specification of mrfa_kp_pose_dist (tests/emu_ext.py): the entry against
+"""The best driving frame from the model's keypoints, on the CPU through the specification of mrfa_kp_pose_dist (oracle/capi_emulator.py on oracle/infer_spec.py): the entry against
 scipy's hull and demo.py:78-94 written out in numpy, collinear and duplicate points, rep, the running argmin, what it refuses, find_best_frame and
-make_animation(initial_frame="best") on the dry model, and a library without the entry."""
+make_animation(initial_frame="best") on the dry model."""
 import numpy as np
 import pytest
 import torch
@@ -8,8 +8,8 @@ import torch
 from mrfa_amd import engine, hip
 from mrfa_amd.infer import Animator, BestFrameSearch, find_best_frame, make_animation, pose_state
 from tests import cases
-from tests.emu import Counting, _Without, emulated_hip
-from tests.emu_ext import ExtEmulator, emulated_hip_ext
+from oracle.capi_emulator import Emulator
+from tests.emu import emulated_hip
 
 CANARY = -1234.5
 PAD = 8
@@ -70,7 +70,7 @@ def _best(state):
 
 def test_specification_against_scipy_and_the_demo_arithmetic():
     ConvexHull = pytest.importorskip("scipy.spatial").ConvexHull
-    emu = ExtEmulator()
+    emu = Emulator()
     for K in (3, 10, 15):
         kd, ks = cases.keypoints(f"best/spec{K}/kd", 20, K)["kp"], cases.keypoints(f"best/spec{K}/ks", 2, K)["kp"]
         rc, dist, area = _entry(emu, kd, ks, rep=10)
@@ -92,7 +92,7 @@ def _lattice():
 
 
 def test_collinear_hull_points_and_duplicates():
-    emu = ExtEmulator()
+    emu = Emulator()
     lattice = _lattice()                                                                         # every edge of the hull carries a third point
     square = torch.tensor([[-0.5, -0.5], [0.0, -0.5], [0.5, -0.5], [0.5, 0.0], [0.5, 0.5], [0.0, 0.5], [-0.5, 0.5], [-0.5, 0.0]])
     for pts, exact in ((lattice, 1.0), (lattice.flip(0), 1.0), (lattice[torch.tensor([4, 0, 8, 1, 2, 6, 3, 7, 5])], 1.0), (square, 1.0),
@@ -121,7 +121,7 @@ def test_collinear_hull_points_and_duplicates():
 
 
 def test_rep_reads_source_n_div_rep():
-    emu, rep = ExtEmulator(), 3
+    emu, rep = Emulator(), 3
     kd, ks = cases.keypoints("best/rep/kd", 6, 15)["kp"], cases.keypoints("best/rep/ks", 2, 15)["kp"]
     rc, dist, area = _entry(emu, kd, ks, rep=rep)
     rc1, dist1, area1 = _entry(emu, kd, ks.repeat_interleave(rep, dim=0).contiguous(), rep=1)
@@ -131,7 +131,7 @@ def test_rep_reads_source_n_div_rep():
 
 
 def test_state_one_call_against_three():
-    emu = ExtEmulator()
+    emu = Emulator()
     kd, ks = cases.keypoints("best/state/kd", 14, 10)["kp"], cases.keypoints("best/state/ks", 2, 10)["kp"]
 
     def run(frames, sizes, sources=ks):
@@ -177,7 +177,7 @@ def test_state_one_call_against_three():
 
 
 def test_entry_refuses_bad_arguments_and_leaves_outputs_and_state_untouched():
-    emu = ExtEmulator()
+    emu = Emulator()
     kd, ks = cases.keypoints("best/bad/kd", 6)["kp"], cases.keypoints("best/bad/ks", 2)["kp"]
     state = pose_state(2, "cpu")
     state[:, 1:] = 77
@@ -202,7 +202,7 @@ def test_entry_refuses_bad_arguments_and_leaves_outputs_and_state_untouched():
 
 def test_ctx_checks_shapes_and_a_recording_context():
     kd, ks = cases.keypoints("best/ctx/kd", 6)["kp"], cases.keypoints("best/ctx/ks", 2)["kp"]
-    with emulated_hip_ext(counting=True) as lib:
+    with emulated_hip(counting=True) as lib:
         e = engine.Ctx(torch.device("cpu"), train=False, record=False)
         launches = lambda: [c for c, _ in lib.calls if c != "mrfa_get_mfma_mode"]                # (the host-side mode query of every new context)
         n = len(launches())
@@ -235,7 +235,7 @@ def _model_and_clips(n):
 
 
 def test_find_best_frame_on_the_dry_model(monkeypatch):
-    with emulated_hip_ext(counting=True) as lib:
+    with emulated_hip(counting=True) as lib:
         m, src, clip = _model_and_clips(5)
         with torch.no_grad():
             ks = m.encoder(src)["kp"].numpy()
@@ -282,7 +282,7 @@ def test_find_best_frame_on_the_dry_model(monkeypatch):
 
 def test_make_animation_best_equals_the_index_it_found():
     """Bs = 1: "best" is the search plus make_animation(initial_frame=that index), bit for bit; the values refused before still raise"""
-    with emulated_hip_ext(counting=True) as lib:
+    with emulated_hip(counting=True) as lib:
         m, src, clip = _model_and_clips(3)
         one_src, one_clip = src[:1].contiguous(), clip[:1].contiguous()
         best = find_best_frame(m, one_src, one_clip)
@@ -301,7 +301,7 @@ def test_make_animation_best_equals_the_index_it_found():
 def test_make_animation_best_finds_the_source_in_the_clip():
     """a clip that holds the source as frame 2: that frame is the best, and the animation from it reproduces the source there"""
     from tests.test_clip_cpu import _gate
-    with emulated_hip_ext():
+    with emulated_hip():
         m, src, clip = _model_and_clips(3)
         clip[:, :, 2] = src
         assert find_best_frame(m, src, clip, frames_per_call=3) == [2, 2]
@@ -313,28 +313,9 @@ def test_make_animation_best_finds_the_source_in_the_clip():
 
 
 def test_make_animation_takes_one_initial_frame_per_source():
-    with emulated_hip_ext():
+    with emulated_hip():
         m, src, clip = _model_and_clips(2)
         c = make_animation(m, src, clip, initial_frame=[0, 1], frames_per_call=2)
         r = make_animation(m, src, clip, initial_frame=0, frames_per_call=2)
         assert torch.equal(c[0], r[0]) and (c[1] - r[1]).abs().max().item() > 1e-3
         assert (c[1, :, 1] - r[1, :, 0]).abs().max().item() <= 1e-3                               # source 1 measured from ITS frame 1: the self-reconstruction there
-
-
-def test_a_library_without_the_entry_says_rebuild(monkeypatch):
-    kd, ks = cases.keypoints("best/old/kd", 6)["kp"], cases.keypoints("best/old/ks", 2)["kp"]
-    assert "mrfa_kp_pose_dist" in hip._EXT_SIGNATURES
-    assert not {"mrfa_kp_pose_dist"} & (set(hip._SIGNATURES) | set(hip.EXPORTED_SYMBOLS) | set(hip.ADDITIVE_SYMBOLS))
-    proxy = Counting(_Without(ExtEmulator(), ("mrfa_kp_pose_dist",)))
-    monkeypatch.setattr(hip, "_lib", proxy)
-    monkeypatch.setattr(hip, "stream_ptr", lambda: 0)
-    assert not hip.has("mrfa_kp_pose_dist") and hip.has("mrfa_kp_relative_fwd")
-    e = engine.Ctx(torch.device("cpu"), train=False, record=False)
-    n = len(proxy.calls)
-    with pytest.raises(RuntimeError, match="rebuild it with"):
-        e.kp_pose_dist(kd, ks, rep=3)
-    assert len(proxy.calls) == n                                                                 # before any launch
-    with emulated_hip():                                                                         # the emulator of include/mrfa_hip.h alone does not have it either
-        assert not hip.has("mrfa_kp_pose_dist")
-    with emulated_hip_ext():
-        assert hip.has("mrfa_kp_pose_dist")

@@ -130,8 +130,8 @@ def test_kernel_against_float64(Bs, T, K):
     Every second-order term is a product of two of these relative errors, each below 1e-3 of its quantity for K <= 64 and A >= 0.05: the factor 1.01 on both
     bounds covers them.  A multiplication and an addition contracted into one fused operation removes a rounding and never adds one.  Nothing is measured.
     Also: two runs are bit-identical (state included), nothing outside the outputs and the state is written, the inputs are not written, the state's index is
-    the float64 argmin (best and second best more than 1e-3 apart), and the CPU specification (tests/emu_ext.py) lies within the same bounds of the kernel."""
-    from tests.emu_ext import ExtEmulator
+    the float64 argmin (best and second best more than 1e-3 apart), and the CPU specification (oracle/capi_emulator.py) lies within the same bounds of the kernel."""
+    from oracle.capi_emulator import Emulator
     kd, ks, replaced = _inputs(Bs, T, K)
     assert replaced == 0 or K < 10, "det_uniform(-0.8, 0.8) with K >= 10 needs no replacement"
     dist64, area64, e_dist, e_area = _bounds(kd, ks, T)
@@ -162,7 +162,7 @@ def test_kernel_against_float64(Bs, T, K):
     assert torch.equal(d2, d) and torch.equal(a2, a)
     # the specification on the same numbers
     e_d, e_a, e_st = torch.full((Bs * T,), CANARY), torch.full((Bs * T,), CANARY), pose_state(Bs, "cpu")
-    assert ExtEmulator().mrfa_kp_pose_dist(0, kd.data_ptr(), ks.data_ptr(), Bs * T, T, K, e_d.data_ptr(), e_a.data_ptr(), e_st.data_ptr()) == 0
+    assert Emulator().mrfa_kp_pose_dist(0, kd.data_ptr(), ks.data_ptr(), Bs * T, T, K, e_d.data_ptr(), e_a.data_ptr(), e_st.data_ptr()) == 0
     assert (np.abs((d.double() - e_d.double()).numpy()) <= e_dist).all() and (np.abs((a.double() - e_a.double()).numpy()) <= e_area).all()
     assert e_st[:, 1:].tolist() == st[:, 1:].tolist()
     assert torch.equal(dkd.cpu(), kd) and torch.equal(dks.cpu(), ks), "inputs must not be written"

@@ -48,7 +48,7 @@ def replicate_cache(cache: dict, t: int) -> dict:
 
 def test_emulator_rep_entry_refuses_its_two_bad_arguments_and_the_parents():
     emu = Emulator()
-    assert emu.mrfa_version() == 11 == hip.ABI_VERSION
+    assert emu.mrfa_version() == hip.ABI_VERSION
     assert "mrfa_corr_direct_rep_fwd" in hip.EXPORTED_SYMBOLS
     q, k0, k1 = torch.randn(4 * 6, 8), torch.randn(16 * 2, 8), torch.randn(4 * 2, 8)
     c, out = torch.zeros(4 * 6, 2), torch.full((4 * 6, 98), 7.0)

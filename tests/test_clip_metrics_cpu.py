@@ -1,5 +1,5 @@
-"""Clip metrics on the CPU through the specification of mrfa_frame_metrics (tests/emu_metrics.py): the specification against a float64 torch restatement
-written with F.conv2d, known values, what the entry and Ctx.frame_metrics refuse, a library without the entry, ClipMetrics, infer.ssim and
+"""Clip metrics on the CPU through the specification of mrfa_frame_metrics (oracle/capi_emulator.py on oracle/infer_spec.py): the specification against a float64 torch restatement
+written with F.conv2d, known values, what the entry and Ctx.frame_metrics refuse, ClipMetrics, infer.ssim and
 reconstruction(metrics="device") on the dry model."""
 import math
 import os
@@ -13,9 +13,10 @@ import torch.nn.functional as F
 from mrfa_amd import engine, hip
 from mrfa_amd.infer import ClipMetrics, psnr, reconstruction, ssim
 from mrfa_amd.utils.prng import det_uniform
-from tests.emu import Counting, _Without, emulated_hip
-from tests.emu_ext import emulated_hip_ext
-from tests.emu_metrics import MetricsEmulator, emulated_hip_metrics
+from oracle import capi_emulator
+from oracle.capi_emulator import Emulator
+from oracle.infer_spec import frame_metrics
+from tests.emu import emulated_hip
 
 CANARY = -1234.5
 PAD = 8
@@ -29,7 +30,7 @@ def torch_window() -> torch.Tensor:
 
 
 def torch_metrics(p: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
-    """the formulas of include/mrfa_hip_ext.h restated in float64 torch with F.conv2d (depthwise, the 2-D outer-product window): (N,4) rows"""
+    """the formulas of include/mrfa_hip.h restated in float64 torch with F.conv2d (depthwise, the 2-D outer-product window): (N,4) rows"""
     p, t = p.double(), t.double()
     C = p.shape[1]
     g = torch_window()
@@ -64,20 +65,18 @@ def _entry(emu, p, t, want_ssim=1, **over):
 
 
 def test_window_constants_of_the_kernel_and_the_tile_in_the_header():
-    """the eleven fp32 literals of csrc/metrics.hip are the formula's numbers, and engine.METRICS_TILE is the header's tile"""
+    """the eleven fp32 literals of csrc/metrics.hip are the formula's numbers, and engine.METRICS_TILE and the emulator's METRICS_TILE are the header's tile"""
     src = open(os.path.join(ROOT, "mrfa_amd", "csrc", "metrics.hip")).read()
     body = re.search(r"GAUSS\[TAPS\]\s*=\s*\{([^}]*)\}", src).group(1)
     lits = [float.fromhex(x.strip().rstrip("f")) for x in body.split(",")]
     assert lits == torch_window().tolist() and len(lits) == 11
-    hdr = open(os.path.join(ROOT, "include", "mrfa_hip_ext.h")).read()
+    hdr = open(os.path.join(ROOT, "include", "mrfa_hip.h")).read()
     tile = tuple(int(re.search(rf"#define MRFA_METRICS_TILE_{k}\s+(\d+)", hdr).group(1)) for k in "HW")
-    assert tile == engine.METRICS_TILE
-    assert {"mrfa_frame_metrics", "mrfa_frame_metrics_workspace"} <= set(hip._EXT_SIGNATURES)
-    assert not {"mrfa_frame_metrics", "mrfa_frame_metrics_workspace"} & (set(hip._SIGNATURES) | set(hip.ADDITIVE_SYMBOLS))
+    assert tile == engine.METRICS_TILE == capi_emulator.METRICS_TILE
+    assert {"mrfa_frame_metrics", "mrfa_frame_metrics_workspace"} <= set(hip.EXPORTED_SYMBOLS)
 
 
 def test_specification_against_the_torch_restatement():
-    from tests.emu_metrics import frame_metrics
     for shape in ((2, 3, 40, 29), (1, 1, 11, 17), (3, 4, 23, 64)):
         for name, (p, t) in families(f"metrics/spec/{shape}", shape).items():
             got = frame_metrics(p.numpy(), t.numpy(), True)
@@ -86,7 +85,7 @@ def test_specification_against_the_torch_restatement():
             print(f"[metrics] specification vs F.conv2d restatement {shape} {name}: max |diff| {err:.2e}, ssim {ref[:, 2].tolist()}")
             assert err <= 1e-12
             assert (frame_metrics(p.numpy(), t.numpy(), False)[:, 2] == 0).all()
-    emu = MetricsEmulator()
+    emu = Emulator()
     p, t = families("metrics/spec/entry", (3, 3, 40, 29))["near"]
     rc, rows = _entry(emu, p, t)
     assert rc == 0 and torch.equal(rows, torch_metrics(p, t).float()) and (rows[:, 3] == 0).all()          # float64 to 1e-12, then the one rounding
@@ -95,13 +94,12 @@ def test_specification_against_the_torch_restatement():
 
 
 def test_known_values():
-    emu = MetricsEmulator()
+    emu = Emulator()
     p = det_uniform("metrics/known/p", (2, 3, 30, 21), 0, 1)
     rc, rows = _entry(emu, p, p.clone())
     assert rc == 0 and (rows[:, :2] == 0).all() and (rows[:, 2].double() - 1).abs().max().item() <= 1e-12
-    from tests.emu_metrics import frame_metrics
     assert np.abs(frame_metrics(p.numpy(), p.numpy(), True)[:, 2] - 1).max() <= 1e-12
-    with emulated_hip_metrics():
+    with emulated_hip():
         cm = ClipMetrics()
         cm.add(p, p.clone())
         res = cm.result()
@@ -123,7 +121,7 @@ def test_known_values():
 
 
 def test_entry_refuses_bad_arguments_before_writing():
-    emu = MetricsEmulator()
+    emu = Emulator()
     p, t = det_uniform("metrics/bad/p", (2, 3, 20, 15), 0, 1), det_uniform("metrics/bad/t", (2, 3, 20, 15), 0, 1)
     rc, rows = _entry(emu, p, t)
     assert rc == 0 and not (rows == CANARY).any()
@@ -152,7 +150,7 @@ def test_entry_refuses_bad_arguments_before_writing():
 
 def test_ctx_frame_metrics_checks_and_a_recording_context():
     p, t = det_uniform("metrics/ctx/p", (2, 3, 20, 15), 0, 1), det_uniform("metrics/ctx/t", (2, 3, 20, 15), 0, 1)
-    with emulated_hip_metrics(counting=True) as lib:
+    with emulated_hip(counting=True) as lib:
         e = engine.Ctx(torch.device("cpu"), train=False, record=False)
         launches = lambda: [c for c, _ in lib.calls if c == "mrfa_frame_metrics"]
         for args, kw in (((p, t[:1]), {}), ((p[0], t[0]), {}), ((p.double(), t.double()), {}), ((p, t.half()), {}), ((p[..., ::2], t[..., ::2]), {}),
@@ -175,29 +173,9 @@ def test_ctx_frame_metrics_checks_and_a_recording_context():
         assert small.shape == (2, 4) and (small[:, 2] == 0).all()
 
 
-def test_a_library_without_the_entry_says_rebuild(monkeypatch):
-    p, t = det_uniform("metrics/old/p", (1, 3, 20, 15), 0, 1), det_uniform("metrics/old/t", (1, 3, 20, 15), 0, 1)
-    proxy = Counting(_Without(MetricsEmulator(), ("mrfa_frame_metrics", "mrfa_frame_metrics_workspace")))
-    monkeypatch.setattr(hip, "_lib", proxy)
-    monkeypatch.setattr(hip, "stream_ptr", lambda: 0)
-    assert not hip.has("mrfa_frame_metrics") and hip.has("mrfa_kp_pose_dist")
-    e = engine.Ctx(torch.device("cpu"), train=False, record=False)
-    n = len(proxy.calls)
-    with pytest.raises(RuntimeError, match="rebuild it with"):
-        e.frame_metrics(p, t)
-    with pytest.raises(RuntimeError, match="rebuild it with"):
-        ClipMetrics().add(p, t)
-    assert [c for c, _ in proxy.calls[n:] if c != "mrfa_get_mfma_mode"] == []        # before any launch
-    for ctx in (emulated_hip, emulated_hip_ext):                                       # the older emulators do not have it either
-        with ctx():
-            assert not hip.has("mrfa_frame_metrics")
-    with emulated_hip_metrics():
-        assert hip.has("mrfa_frame_metrics") and hip.has("mrfa_kp_pose_dist")
-
-
 def test_clip_metrics_groups_equal_one_group(monkeypatch):
     p, t = families("metrics/groups", (7, 3, 24, 19))["near"]
-    with emulated_hip_metrics(counting=True) as lib:
+    with emulated_hip(counting=True) as lib:
         reads = []
         real = torch.Tensor.cpu
         monkeypatch.setattr(torch.Tensor, "cpu", lambda self, *a, **k: (reads.append("cpu"), real(self, *a, **k))[1])
@@ -221,7 +199,7 @@ def test_clip_metrics_groups_equal_one_group(monkeypatch):
 def test_reconstruction_device_metrics_on_the_dry_model():
     from tests.test_bf16_cache import _dry_model
     from tests.test_clip_cpu import _clips
-    with emulated_hip_metrics(counting=True) as lib:
+    with emulated_hip(counting=True) as lib:
         m = _dry_model()
         _, clip = _clips(4)
         host = reconstruction(m, clip, frames_per_call=3)

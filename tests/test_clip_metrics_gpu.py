@@ -7,7 +7,8 @@ import torch
 
 from mrfa_amd import engine, hip
 from mrfa_amd.utils.prng import det_uniform
-from tests.emu_metrics import C1, C2, MetricsEmulator, _window, gauss_window
+from oracle.capi_emulator import Emulator
+from oracle.infer_spec import C1, C2, _window, gauss_window
 
 pytestmark = pytest.mark.gpu
 
@@ -134,15 +135,15 @@ def _check(family, shape, want_ssim=True):
         assert (got[:, 2] == 0).all()
     # the specification on the same numbers: float64, then ITS one rounding
     spec = torch.full((p.shape[0], 4), CANARY)
-    ws = torch.zeros(max(MetricsEmulator().mrfa_frame_metrics_workspace(*shape) // 8, 1), dtype=torch.float64)
-    assert MetricsEmulator().mrfa_frame_metrics(0, p.data_ptr(), t.data_ptr(), *shape, int(want_ssim), ws.data_ptr(), ws.numel() * 8, spec.data_ptr()) == 0
+    ws = torch.zeros(max(Emulator().mrfa_frame_metrics_workspace(*shape) // 8, 1), dtype=torch.float64)
+    assert Emulator().mrfa_frame_metrics(0, p.data_ptr(), t.data_ptr(), *shape, int(want_ssim), ws.data_ptr(), ws.numel() * 8, spec.data_ptr()) == 0
     assert (np.abs((got.double() - spec.double()).numpy()) <= bound + U * np.abs(rows64)).all()
     return got, rows64, bound
 
 
 @pytest.mark.parametrize("shape", SSIM_SHAPES, ids=lambda s: "x".join(map(str, s)))
 def test_kernel_against_float64(shape):
-    """u = 2^-24; the inputs are fp32 numbers in [0, 1], the expected values float64 on the same numbers (tests/emu_metrics.py's window sums with the
+    """u = 2^-24; the inputs are fp32 numbers in [0, 1], the expected values float64 on the same numbers (oracle/infer_spec.py's window sums with the
     eleven fp32 weights in float64).  The kernel's roundings in its own order, first order in u; a multiplication and an addition contracted into one fused
     operation removes a rounding and never adds one.  Nothing is measured from the kernel.
 

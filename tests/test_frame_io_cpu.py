@@ -1,5 +1,5 @@
-"""Frames as bytes on the CPU through the specification of mrfa_frames_from_u8 / mrfa_frames_to_u8 (tests/emu_frames.py): the conversions and the Visualizer
-grid against numpy written here from the rules of include/mrfa_hip_ext.h, the wiring of make_animation / reconstruction / Animator on the dry model, and
+"""Frames as bytes on the CPU through the specification of mrfa_frames_from_u8 / mrfa_frames_to_u8 (oracle/capi_emulator.py on oracle/infer_spec.py): the conversions and the Visualizer
+grid against numpy written here from the rules of include/mrfa_hip.h, the wiring of make_animation / reconstruction / Animator on the dry model, and
 what the entries, Ctx and the public functions refuse."""
 import sys
 
@@ -11,9 +11,8 @@ from mrfa_amd import engine, hip
 from mrfa_amd.engine import FrameTile
 from mrfa_amd.infer import Animator, BestFrameSearch, Visualizer, frames_from_uint8, frames_to_uint8, make_animation, reconstruction
 from mrfa_amd.utils.prng import det_uniform
-from tests.emu import Counting, _Without
-from tests.emu_frames import FramesEmulator, emulated_hip_frames
-from tests.emu_metrics import emulated_hip_metrics
+from oracle.capi_emulator import Emulator
+from tests.emu import emulated_hip
 
 FILL = 0x5A
 
@@ -85,7 +84,7 @@ def np_column(x, kp, radius, colors, border, rounding) -> np.ndarray:
 # --------------------------------------------------------------------------------------------------------------------- conversions
 @pytest.mark.parametrize("cin", [1, 3, 4])
 def test_frames_from_uint8_is_one_multiply(cin):
-    with emulated_hip_frames(counting=True) as lib:
+    with emulated_hip(counting=True) as lib:
         u8 = bytes_of(f"fio/from/{cin}", (8, 5, 7, cin))
         u8.view(-1)[:256] = torch.arange(256, dtype=torch.uint8)           # every byte value
         got = frames_from_uint8(u8)
@@ -108,7 +107,7 @@ def test_frames_to_uint8_rounds_and_clamps(rounding):
     special = torch.tensor([0.0, -0.0, 1.0, -1e-3, 1.001, float("nan"), float("inf"), -float("inf")])
     x.view(-1)[:255] = torch.from_numpy(ties)
     x.view(-1)[255:263] = special
-    with emulated_hip_frames():
+    with emulated_hip():
         got = frames_to_uint8(x, rounding)
         assert got.dtype == torch.uint8 and got.shape == (2, 6, 9, 3)
         assert torch.equal(got, torch.from_numpy(np_to_u8(x.numpy(), rounding)))
@@ -137,7 +136,7 @@ def test_visualizer_grid_against_numpy(border):
     kp_s, kp_d = draw_keypoints("fio/viz/kps", N, K, H, W, R, fix=placed), draw_keypoints("fio/viz/kpd", N, K, H, W, R)
     assert margin_ok(kp_s.numpy(), H, W, R) and margin_ok(kp_d.numpy(), H, W, R)
     colors = det_uniform("fio/viz/colors", (K, 3), 0, 1)
-    with emulated_hip_frames(counting=True) as lib:
+    with emulated_hip(counting=True) as lib:
         viz = Visualizer(draw_border=border, kp_size=R, colors=colors.numpy())
         assert viz.rounding == "floor"
         grid = viz.visualize(drv, src, out, kp_s={"kp": kp_s}, kp_d=kp_d)
@@ -162,7 +161,7 @@ def test_visualizer_colours_need_matplotlib_or_colors(monkeypatch):
     kp = torch.zeros(1, 4, 2)
     monkeypatch.setitem(sys.modules, "matplotlib", None)                    # absent, wherever this runs
     monkeypatch.setitem(sys.modules, "matplotlib.pyplot", None)
-    with emulated_hip_frames():
+    with emulated_hip():
         with pytest.raises(RuntimeError, match=r"colors=.*\(4,3\)"):
             Visualizer().visualize(src, src, src, kp_s=kp)
         assert Visualizer().visualize(src, src, src).shape == (8, 24, 3)    # without keypoints no colours are needed
@@ -182,7 +181,7 @@ def test_visualizer_colours_need_matplotlib_or_colors(monkeypatch):
 def dry():
     from tests.test_bf16_cache import _dry_model
     from tests.test_clip_cpu import _clips
-    with emulated_hip_frames():
+    with emulated_hip():
         m = _dry_model()
     src, clip = _clips(4)
     return m, src, clip
@@ -190,7 +189,7 @@ def dry():
 
 def test_make_animation_uint8_output_and_input(dry):
     m, src, clip = dry
-    with emulated_hip_frames(counting=True) as lib:
+    with emulated_hip(counting=True) as lib:
         base = make_animation(m, src, clip, relative=True, frames_per_call=3)
         assert torch.equal(base, make_animation(m, src, clip, relative=True, frames_per_call=3, output="float")) and base.dtype == torch.float32
         assert not [c for c, _ in lib.calls if c.startswith("mrfa_frames_")]          # the defaults do not touch the new entries
@@ -213,7 +212,7 @@ def test_make_animation_uint8_output_and_input(dry):
 def test_reconstruction_uint8_output_and_visualization(dry):
     m, _, clip = dry
     B, _, T, H, W = clip.shape
-    with emulated_hip_frames():
+    with emulated_hip():
         for metrics in ("host", "device"):
             base = reconstruction(m, clip, frames_per_call=3, metrics=metrics)
             same = reconstruction(m, clip, frames_per_call=3, metrics=metrics, output="float", visualize=False)
@@ -242,7 +241,7 @@ def test_animator_and_best_frame_take_bytes(dry):
     m, _, _ = dry
     B, H, W = 2, 64, 64
     src8, drv8 = bytes_of("fio/an/src8", (B, H, W, 3)), bytes_of("fio/an/drv8", (2 * B, H, W, 3))
-    with emulated_hip_frames(counting=True) as lib:
+    with emulated_hip(counting=True) as lib:
         a8, af = Animator(m, relative=True), Animator(m, relative=True)
         a8.set_source(src8, drv8[::2].contiguous())
         af.set_source(frames_from_uint8(src8), frames_from_uint8(drv8[::2].contiguous()))
@@ -275,7 +274,7 @@ def _tile(src, **kw):
 
 
 def test_entries_refuse_before_writing():
-    emu = FramesEmulator()
+    emu = Emulator()
     u8 = bytes_of("fio/bad/u8", (1, 4, 6, 3))
     dst = torch.full((1, 3, 4, 6), -7.0)
     for bad, word in ((dict(Cin=2), b"not 2"), (dict(Cin=5), b"not 5"), (dict(N=0), b"N 0"), (dict(W=-1), b"W -1"), (dict(src=None), b"null"),
@@ -315,7 +314,7 @@ def test_entries_refuse_before_writing():
 def test_ctx_and_public_functions_refuse_with_the_offending_value():
     x = det_uniform("fio/ctx/x", (2, 3, 4, 6), 0, 1)
     u8 = bytes_of("fio/ctx/u8", (2, 4, 6, 3))
-    with emulated_hip_frames(counting=True) as lib:
+    with emulated_hip(counting=True) as lib:
         e = engine.Ctx(torch.device("cpu"), train=False, record=False)
         for bad, msg in ((u8.float(), "float32"), (u8.int(), "int32"), (u8[..., :2], r"\(2, 4, 6, 2\)"), (u8[0, 0], r"\(6, 3\)"), (u8.numpy(), "ndarray")):
             with pytest.raises(ValueError, match=msg):
@@ -355,29 +354,12 @@ def test_ctx_and_public_functions_refuse_with_the_offending_value():
         assert np.array_equal(got[:, 1:, 7:].numpy(), np_to_u8(x.numpy(), "floor"))
 
 
-def test_a_library_without_the_entries_says_rebuild(monkeypatch):
-    names = ("mrfa_frames_from_u8", "mrfa_frames_to_u8")
-    assert set(names) <= set(hip._EXT_SIGNATURES) and not set(names) & (set(hip._SIGNATURES) | set(hip.ADDITIVE_SYMBOLS)) and hip.ABI_VERSION == 11
-    proxy = Counting(_Without(FramesEmulator(), names))
-    monkeypatch.setattr(hip, "_lib", proxy)
-    monkeypatch.setattr(hip, "stream_ptr", lambda: 0)
-    assert not hip.has(names[0]) and hip.has("mrfa_frame_metrics")
-    with pytest.raises(RuntimeError, match="mrfa_frames_from_u8.*rebuild it with"):
-        frames_from_uint8(torch.zeros(1, 2, 2, 3, dtype=torch.uint8))
-    with pytest.raises(RuntimeError, match="mrfa_frames_to_u8.*rebuild it with"):
-        frames_to_uint8(torch.zeros(1, 3, 2, 2))
-    assert not [c for c, _ in proxy.calls if c.startswith("mrfa_frames_")]
-    with emulated_hip_metrics():                                                            # the older emulator does not have them either
-        assert not hip.has(names[0])
-    with emulated_hip_frames():
-        assert hip.has(names[0]) and hip.has(names[1]) and hip.has("mrfa_kp_pose_dist")
-
-
 def test_the_header_and_the_binding_agree():
+    assert {"mrfa_frames_from_u8", "mrfa_frames_to_u8"} <= set(hip.EXPORTED_SYMBOLS)
     import ctypes as C
     import os
     import re
-    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "mrfa_hip_ext.h")).read()
+    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "mrfa_hip.h")).read()
     assert int(re.search(r"#define MRFA_U8_MAX_TILES\s+(\d+)", hdr).group(1)) == hip.U8_MAX_TILES == 8
     assert int(re.search(r"#define MRFA_U8_MAX_KP\s+(\d+)", hdr).group(1)) == hip.U8_MAX_KP == 64
     body = re.search(r"typedef struct \{([^}]*)\} mrfa_u8_tile;", hdr).group(1)

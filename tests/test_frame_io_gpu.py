@@ -9,7 +9,7 @@ from mrfa_amd import hip
 from mrfa_amd.engine import Ctx, FrameTile
 from mrfa_amd.infer import Animator, frames_from_uint8, frames_to_uint8, make_animation, reconstruction
 from mrfa_amd.utils.prng import det_uniform
-from tests.emu_frames import FramesEmulator
+from oracle.capi_emulator import Emulator
 from tests.test_frame_io_cpu import FILL, bytes_of, draw_keypoints, margin_ok, np_column, np_from_u8, np_to_u8
 
 pytestmark = pytest.mark.gpu
@@ -222,7 +222,7 @@ def test_disc_at_the_exact_centre():
 
 # --------------------------------------------------------------------------------------------------------------------- the emulator and the kernels
 def test_emulator_equals_the_kernels():
-    emu = FramesEmulator()
+    emu = Emulator()
     u8 = bytes_of("fio/gpu/emu/u8", (2, 6, 10, 4))
     spec = torch.full((2, 3, 6, 10), -1.0)
     assert emu.mrfa_frames_from_u8(0, u8.data_ptr(), 2, 6, 10, 4, spec.data_ptr()) == 0

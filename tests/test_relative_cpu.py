@@ -154,28 +154,10 @@ def test_make_animation_is_one_animator_loop_that_reaches_the_entry():
                 make_animation(m, src, clip, initial_frame=bad)
 
 
-def test_a_library_without_the_entry_runs_the_torch_form_and_says_so():
-    """the emulator without the entry stands for a version-11 library built before it: hip.has() is False, Ctx.kp_relative warns once per process and
-    computes normalize_kp's own operations (bit for bit its result on repeated inputs); a misaligned view is copied, not refused"""
-    from mrfa_amd import engine
-    from mrfa_amd.infer import normalize_kp
+def test_a_misaligned_jacobian_view_is_copied_not_refused():
+    """an operand at an offset the kernel's float4 loads cannot take is copied first: one launch, the aligned operand's result bit for bit"""
     kd, k0, ks = cases.keypoints("rel/old/kd", 6), cases.keypoints("rel/old/k0", 2), cases.keypoints("rel/old/ks", 2)
-    scale = torch.tensor([0.37])
-    ri = lambda d: {k: v.repeat_interleave(3, dim=0) for k, v in d.items()}
-    ref = normalize_kp(ri(ks), kd, ri(k0), use_relative_movement=True, use_relative_jacobian=True)
-    ref_kp = (kd["kp"] - ri(k0)["kp"]) * scale + ri(ks)["kp"]
-    with emulated_hip(without=("mrfa_kp_relative_fwd",)):
-        assert not hip.has("mrfa_kp_relative_fwd")
-        engine.Ctx._warned_no_kp_relative = False
-        with pytest.warns(RuntimeWarning, match="no mrfa_kp_relative_fwd"):
-            r = relative_kp(ks, kd, k0, scale=scale, rep=3)
-        assert torch.equal(r["kp"], ref_kp) and torch.equal(r["jacobian"], ref["jacobian"])
-        import warnings
-        with warnings.catch_warnings():
-            warnings.simplefilter("error")                                            # once per process
-            assert torch.equal(relative_kp(ks, kd, k0, rep=3)["kp"], ref["kp"])
     with emulated_hip(counting=True) as lib:
-        assert hip.has("mrfa_kp_relative_fwd")
         flat = torch.zeros(6 * 10 * 4 + 1)
         odd = dict(kd, jacobian=flat[1:].view(6, 10, 2, 2).copy_(kd["jacobian"]))     # 4 bytes past a 16-byte boundary
         assert odd["jacobian"].data_ptr() % 16 == 4
