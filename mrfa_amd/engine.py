@@ -69,6 +69,13 @@ def mark(name: str):
     m.names.append(name)
 
 
+class _Deferred(NamedTuple):
+    """one launch of a DeferredWgrads collection"""
+    fn: Callable[[], None]
+    params: Optional[hip.WgradParams] = None     # the block of a plain weight-gradient call (mrfa_conv2d_wgrad_nhwc): batch mode issues it from there, not by fn
+    keep: tuple = ()                             # what the launch reads: alive until join()
+
+
 class DeferredWgrads:
     """The weight-gradient launches of the programs recorded under `defer_wgrads(d)` (dense motion + RaftFlow: ~100 launches, 22 ms of
     kernels that fill the chip) are not issued where the backward tape reaches them but collected, and issued on ONE side stream when
@@ -82,9 +89,9 @@ class DeferredWgrads:
         # manual: flushed only by join() (never by the backward of the next program): the keypoint encoder's collection -- its programs run their
         # backward on several streams, and only HotPath.join() has ordered all of them before the stream the flush forks from
         self.manual = manual
-        self.thunks: List[Callable[[], None]] = []
-        self.finals: List[Callable[[], None]] = []          # run after every thunk (the un-packing of the accumulators they add into)
-        self.kept: Optional[List[Callable[[], None]]] = None
+        self.thunks: List[_Deferred] = []
+        self.finals: List[_Deferred] = []                    # run after every thunk (the un-packing of the accumulators they add into)
+        self.kept: Optional[List[_Deferred]] = None
         self.stream: Optional["torch.cuda.Stream"] = None
         self.fan: List["torch.cuda.Stream"] = []
         # > 1: the launches are dealt round-robin onto that many side streams (the keypoint encoder's ~400 small weight-gradient launches,
@@ -95,8 +102,8 @@ class DeferredWgrads:
         self._rr = 0
         self._used: List["torch.cuda.Stream"] = []           # side streams that received launches since the last join
         self._srcs: List["torch.cuda.Stream"] = []           # streams on which the pending launches were collected
-    def add(self, fn: Callable[[], None], final: bool = False):
-        (self.finals if final else self.thunks).append(fn)
+    def add(self, fn: Callable[[], None], final: bool = False, params: Optional[hip.WgradParams] = None, keep: tuple = ()):
+        (self.finals if final else self.thunks).append(_Deferred(fn, params, keep))
         if torch.cuda.is_available():
             # the launch reads what the CURRENT stream has produced (dY of this layer): a program may run part of its backward on a branch
             # stream (Ctx.branch), so the side streams wait for every stream that contributed, not only for the one that flushes
@@ -123,18 +130,9 @@ class DeferredWgrads:
             self.fan.append(torch.cuda.Stream(device=dev))
         return [self.stream] + self.fan[:self.fanout - 1]
 
-    def _deal(self, dev: torch.device):
+    def _deal(self, dev: torch.device, plain: List[_Deferred], todo: List[_Deferred]):
         """issue the collected launches on the side streams, ordered after the current stream; the streams are joined by flush()"""
         if not self.thunks:
-            return
-        if dev.type != "cuda":                               # (the ABI emulator: no streams; the same marshalling as below, so that it is tested without a GPU)
-            todo = self.thunks
-            if self.batch:
-                todo = [fn for fn in self.thunks if getattr(fn, "params", None) is None]
-                self._issue_plain([fn for fn in self.thunks if getattr(fn, "params", None) is not None], dev)
-            for fn in todo:
-                fn()
-            self.thunks = []
             return
         cur = torch.cuda.current_stream(dev)
         lanes = self._lanes(dev) if len(self.thunks) > self.fanout else self._lanes(dev)[:1]
@@ -145,21 +143,13 @@ class DeferredWgrads:
                     st.wait_stream(src)
             if st not in self._used:
                 self._used.append(st)
-        todo = self.thunks
-        if self.batch:
-            # launches that are plain weight-gradient calls travel as ONE parameter array per side stream (mrfa_conv2d_wgrad_multi: the problems the
-            # small-problem kernel takes then run up to 28 per launch); the two-stage scratch is per stream, so it is re-pointed like launch() does
-            plain = [fn for fn in todo if getattr(fn, "params", None) is not None]
-            todo = [fn for fn in todo if getattr(fn, "params", None) is None]
-            for k, st in enumerate(lanes):
-                mine = plain[k::len(lanes)]
-                if not mine:
-                    continue
+        for k, st in enumerate(lanes):
+            if plain[k::len(lanes)]:
                 with torch.cuda.stream(st):
-                    self._issue_plain(mine, dev)
-        for fn in todo:
+                    self._issue_plain(plain[k::len(lanes)], dev)
+        for t in todo:
             with torch.cuda.stream(lanes[self._rr % len(lanes)]):
-                fn()
+                t.fn()
             self._rr += 1
         # the closures own the buffers the side streams are still reading -- ALL flushes of the step (a collection can be flushed more than once:
         # the third encoder pass of the reference objective finishes its backward before the decoder's starts) until join() / reset()
@@ -168,31 +158,35 @@ class DeferredWgrads:
         self.flushed = True
 
     @staticmethod
-    def _issue_plain(fns, dev: torch.device):
+    def _issue_plain(plain, dev: torch.device):
         """the parameter blocks of plain weight-gradient launches as ONE array on the current stream (mrfa_conv2d_wgrad_multi)"""
-        if not fns:
+        if not plain:
             return
         sp = hip.stream_ptr()
         ws = Ctx._wgrad_scratch(dev, sp)
-        arr = (hip.WgradParams * len(fns))()
-        for i, fn in enumerate(fns):
-            C.memmove(C.byref(arr, i * C.sizeof(hip.WgradParams)), C.byref(fn.params), C.sizeof(hip.WgradParams))
+        arr = (hip.WgradParams * len(plain))()
+        for i, t in enumerate(plain):
+            C.memmove(C.byref(arr, i * C.sizeof(hip.WgradParams)), C.byref(t.params), C.sizeof(hip.WgradParams))
             arr[i].ws, arr[i].ws_bytes = ws.data_ptr(), ws.numel() * 4
-        hip.check(hip.lib().mrfa_conv2d_wgrad_multi(sp, arr, len(fns)), "wgrad_multi(deferred)")
+        hip.check(hip.lib().mrfa_conv2d_wgrad_multi(sp, arr, len(plain)), "wgrad_multi(deferred)")
 
     def flush(self, dev: torch.device):
         """issue everything collected so far on the side streams, ordered after the current stream; then the finals on the first of them, after all"""
         if not self.thunks and not self.finals:
             return
-        if dev.type != "cuda":
-            self._deal(dev)
-            for fn in self.finals:
-                fn()
-            self.finals = []
+        # launches that are plain weight-gradient calls travel as ONE parameter array per side stream (mrfa_conv2d_wgrad_multi: the problems the
+        # small-problem kernel takes then run up to 28 per launch); the two-stage scratch is per stream, so it is re-pointed like launch() does
+        plain = [t for t in self.thunks if self.batch and t.params is not None]
+        todo = [t for t in self.thunks if not self.batch or t.params is None]
+        if dev.type != "cuda":                               # (the ABI emulator: no streams; the same marshalling as below, so that it is tested without a GPU)
+            self._issue_plain(plain, dev)
+            for t in todo + self.finals:
+                t.fn()
+            self.thunks, self.finals = [], []
             return
         tag = "enc wgrads" if self.manual else "dec wgrads"
         mark(tag + ": flush")
-        self._deal(dev)
+        self._deal(dev, plain, todo)
         self._lanes(dev)
         self.stream.wait_stream(torch.cuda.current_stream(dev))
         for st in self._used + self._srcs:
@@ -202,8 +196,8 @@ class DeferredWgrads:
         if self.stream not in self._used:
             self._used.append(self.stream)
         with torch.cuda.stream(self.stream):
-            for fn in self.finals:
-                fn()
+            for t in self.finals:
+                t.fn()
             mark(tag + ": done")
         self.kept = (self.kept or []) + self.finals
         self.finals = []
@@ -222,19 +216,19 @@ WGRAD_DEFER: Optional[DeferredWgrads] = None           # programs whose forward 
 _PENDING_DEFERRED: List[DeferredWgrads] = []            # collections with thunks not yet issued
 
 
-class defer_wgrads:
-    def __init__(self, d: Optional[DeferredWgrads]):
-        self.d = d
+@contextlib.contextmanager
+def _module_value(name: str, value):
+    """with _module_value(name, v): the module-level value `name` is v inside, and what it was before afterwards"""
+    g = globals()
+    prev, g[name] = g[name], value
+    try:
+        yield value
+    finally:
+        g[name] = prev
 
-    def __enter__(self):
-        global WGRAD_DEFER
-        self.prev, WGRAD_DEFER = WGRAD_DEFER, self.d
-        return self.d
 
-    def __exit__(self, *exc):
-        global WGRAD_DEFER
-        WGRAD_DEFER = self.prev
-        return False
+def defer_wgrads(d: Optional[DeferredWgrads]):
+    return _module_value("WGRAD_DEFER", d)
 
 
 SYNCBN_FORCE = os.environ.get("MRFA_SYNCBN_FORCE_COLLECTIVE", "0") == "1"
@@ -325,30 +319,13 @@ class FrameTile(NamedTuple):
     border: bool = False
 
 
-class stat_groups:
+def stat_groups(groups: int):
     """with stat_groups(g): programs started inside treat their batch as g statistic groups of N / g consecutive samples"""
-
-    def __init__(self, groups: int):
-        self.groups = int(groups)
-
-    def __enter__(self):
-        global STAT_GROUPS
-        self.prev, STAT_GROUPS = STAT_GROUPS, self.groups
-
-    def __exit__(self, *exc):
-        global STAT_GROUPS
-        STAT_GROUPS = self.prev
-        return False
+    return _module_value("STAT_GROUPS", int(groups))
 
 
-class direct_param_grads:
-    def __enter__(self):
-        global DIRECT_PARAM_GRADS
-        self.prev, DIRECT_PARAM_GRADS = DIRECT_PARAM_GRADS, True
-
-    def __exit__(self, *exc):
-        global DIRECT_PARAM_GRADS
-        DIRECT_PARAM_GRADS = self.prev
+def direct_param_grads():
+    return _module_value("DIRECT_PARAM_GRADS", True)
 
 
 def _direct_ok(*params) -> bool:
@@ -395,9 +372,8 @@ class Storage:
         # applies the ReLU mask (fused into its epilogue where the library can, a masking pass of its own otherwise), so the
         # producers skip their ReLU-backward pass
         self.bwd_masked = False
-        # not None: the buffer is the output of a BatchNorm + activation with ONE consumer, a convolution (Ctx.bn_act(out_sole=True)): what that
-        # convolution's data gradient needs to accumulate the first phase of the BatchNorm's backward in its epilogue (Ctx._conv_dgrad)
-        self.bn_hint = None
+        # not None: the buffer is the output of a BatchNorm + activation with ONE consumer, a convolution (Ctx.bn_act(out_sole=True))
+        self.bn_hint: Optional[BnHint] = None
         # position of this buffer among its program's forward activations and that program's zero plan (Ctx.zero_plan): a gradient buffer that had to be
         # zero-filled on first touch is remembered there, and the next run of the same program zero-fills all such buffers in ONE multi-tensor launch
         self.seq = -1
@@ -797,6 +773,58 @@ class IslandOut:
         return g
 
 
+# ------------------------------------------------------------------------------------------------- BatchNorm records
+class BnVectors(NamedTuple):
+    """the result of a BatchNorm finalize: four [groups][C] fp32 vectors (Ctx._bn_vectors allocates them)"""
+    scale: torch.Tensor
+    shift: torch.Tensor
+    mean: torch.Tensor
+    invstd: torch.Tensor
+    groups: int
+
+    def ptrs(self):
+        """(scale, shift, mean, invstd) as device pointers, the order in which every parameter block of the ABI lists them"""
+        return tuple(t.data_ptr() for t in self[:4])
+
+
+class BnHint:
+    """what the data gradient of the ONE convolution that consumes act(bn(x)) needs to accumulate the first phase of the BatchNorm's backward in its
+    epilogue (Ctx._conv_dgrad).  red: None until such a launch has done so; then the sums, and Ctx._bn_bwd runs phase 2 only."""
+    __slots__ = ("x", "v", "relu", "red")
+
+    def __init__(self, x: View, v: BnVectors, relu: bool):
+        self.x, self.v, self.relu, self.red = x, v, relu, None
+
+
+class Prologue:
+    """what Ctx.prebn() returns and conv(pre=) takes: relu(scale * x + shift) applied by the consuming convolution's forward, data gradient and weight
+    gradient.  scale, shift: device pointers of [groups][Cin] vectors (`vectors` owns them; a capability query has placeholders and none).  dz, ups:
+    filled by that convolution's data gradient (d(relu(bn(x))) as data), read by prebn()'s backward closure, which runs after it."""
+    __slots__ = ("scale", "shift", "groups", "hint", "vectors", "dz", "ups")
+
+    def __init__(self, scale: int, shift: int, groups: int, hint: Optional[BnHint] = None, vectors: Optional[BnVectors] = None):
+        self.scale, self.shift, self.groups, self.hint, self.vectors = scale, shift, groups, hint, vectors
+        self.dz, self.ups = None, False
+
+
+class SyncGroup:
+    """the SyncBatchNorm layers of one Ctx.sync_stats() call, for their backward passes.  left: members whose first phase is still to run (or to be
+    skipped); pending: (parameter block, sums) of those that ran it; red: statistics pointer -> a member's sums, until its bn_act() takes them."""
+
+    def __init__(self):
+        self.left, self.pending, self.red = 0, [], {}
+
+    def member_done(self, ctx: "Ctx"):
+        """one member has run (or skipped) the first phase of its backward; the last one exchanges all the sums and runs every second phase"""
+        self.left -= 1
+        if self.left > 0 or not self.pending:
+            return
+        _syncbn_all_reduce_many([red for _, red in self.pending])
+        for q, _ in self.pending:
+            ctx._chk(ctx.L.mrfa_bn_act_bwd(ctx.s, C.byref(q)), "bn_act_bwd(2)")
+        self.pending = []
+
+
 # ------------------------------------------------------------------------------------------------- the op context
 class Ctx:
     # bench.py sets this to a list to collect (config, flops, start_event, end_event) per MFMA conv/GEMM launch
@@ -830,6 +858,7 @@ class Ctx:
         # instead of ~100 fill launches scattered over the backward chains (tools/trace_fills.py: 121 fills per step, ~10 us each on the critical path)
         self.zero_plan: Optional[set] = None
         self._rs = None                    # fused_resizes(): the copies / resizes recorded for one launch
+        self.side_used = False             # weight gradients of this backward pass were issued on Ctx._side (WGRAD_STREAM)
 
     # -- plumbing
     @property
@@ -1032,7 +1061,7 @@ class Ctx:
     # -- convolution ------------------------------------------------------------------------------------------
     def conv(self, x: View, conv: torch.nn.Conv2d, out: Optional[View] = None, *, relu=False, ups=False, pre=None,
              stats: Optional[torch.Tensor] = None, res: Optional[View] = None, need_dx=True, use_bias=True, relu_in=False, fin=None) -> View:
-        """y = conv(pre(ups(x))) (+bias)(+res)(ReLU).  pre = (scale, shift) tensors of a pre-activation BN+ReLU.
+        """y = conv(pre(ups(x))) (+bias)(+res)(ReLU).  pre = the Prologue of a pre-activation BN+ReLU (prebn()).
         fin: the BatchNorm that follows (with `stats`): finished inside the convolution call (mrfa_conv_params.fin_*, see _fin_params).
         relu_in: the caller states that x (all of its storage) holds ReLU outputs and that this conv is their only consumer: the ReLU
         backward of x's producers then rides in this conv's data gradient (mrfa_conv_params.mask) instead of a pass of its own."""
@@ -1084,7 +1113,7 @@ class Ctx:
         p.Cout, p.Hout, p.Wout = cw.Cout, Ho, Wo
         p.R, p.S, p.pad = cw.R, cw.S, cw.pad
         if pre is not None:
-            p.in_scale, p.in_shift, p.in_relu = pre[0].data_ptr(), pre[1].data_ptr(), 1
+            p.in_scale, p.in_shift, p.in_relu = pre.scale, pre.shift, 1
             if self.train and self.groups > 1:        # (v9: the prologue vectors are [groups][Cin]; prologue_ok() asked the library)
                 p.groups = self.groups
         p.bias = bias.data_ptr() if bias is not None else None
@@ -1154,12 +1183,12 @@ class Ctx:
         return False
 
     @staticmethod
-    def _wgrad_params(x: View, cw: ConvW, dy: int, ldy: int, Ho: int, Wo: int, dw: int, ups=False, stride: int = 0, pre=None) -> hip.WgradParams:
-        """the parameter block of cw's weight gradient from x and dY; pre: (in_scale, in_shift, groups) of a prologue, as pointers"""
+    def _wgrad_params(x: View, cw: ConvW, dy: int, ldy: int, Ho: int, Wo: int, dw: int, ups=False, stride: int = 0, pre: Optional[Prologue] = None) -> hip.WgradParams:
+        """the parameter block of cw's weight gradient from x and dY"""
         q = hip.WgradParams()
         q.x, q.ldx, q.Hin, q.Win, q.ups, q.N, q.Cin = x.ptr, x.ld, x.H, x.W, int(ups), x.N, cw.Cin
         if pre is not None:
-            q.in_scale, q.in_shift, q.in_relu, q.groups = pre[0], pre[1], 1, pre[2]
+            q.in_scale, q.in_shift, q.in_relu, q.groups = pre.scale, pre.shift, 1, pre.groups
         q.dy, q.ldy, q.Cout, q.Hout, q.Wout = dy, ldy, cw.Cout, Ho, Wo
         q.R, q.S, q.pad, q.stride = cw.R, cw.S, cw.pad, stride
         q.dw, q.alpha, q.nbatch, q.ksplit = dw, 1.0, 1, 0
@@ -1205,8 +1234,7 @@ class Ctx:
 
     def _conv_wgrad(self, x: View, cw: ConvW, out: View, ups, pre, has_bias):
         dw, db = cw.grad_acc(self.pool32)
-        q = self._wgrad_params(x, cw, out.gptr, out.ld, out.H, out.W, dw.data_ptr(), ups,
-                               pre=pre and (pre[0].data_ptr(), pre[1].data_ptr(), pre[2].get("groups", 1)))
+        q = self._wgrad_params(x, cw, out.gptr, out.ld, out.H, out.W, dw.data_ptr(), ups, pre=pre)
         q.dbias = db.data_ptr() if (has_bias and db is not None) else None
         if cw.wgrad_flat:
             q.ktab, q.kflat = cw.ktab_fwd().data_ptr(), cw.T * cw.Cin
@@ -1214,17 +1242,13 @@ class Ctx:
         q.ws, q.ws_bytes = ws.data_ptr(), ws.numel() * 4
         prof = Ctx.profile
         if prof is None and self._defer_ok(cw):
-            keep = (x, out, pre, dw, db)                   # alive until DeferredWgrads.join()
-
             def launch():
                 st = hip.stream_ptr()
                 w2 = self._wgrad_scratch(self.dev, st)
                 q.ws, q.ws_bytes = w2.data_ptr(), w2.numel() * 4
-                assert keep[0].st.data is not None
                 self._chk(self.L.mrfa_conv2d_wgrad_nhwc(st, C.byref(q)), "wgrad(deferred)")
-            launch.params = q                              # DeferredWgrads batches such launches (mrfa_conv2d_wgrad_multi)
-            launch.keep = keep
-            self.wdefer.add(launch)
+            # (DeferredWgrads batches launches that come with their block: mrfa_conv2d_wgrad_multi; what the block points into stays alive until join())
+            self.wdefer.add(launch, params=q, keep=(x, out, pre, dw, db))
         elif prof is None and WGRAD_STREAM:
             main = torch.cuda.current_stream(self.dev)
             if Ctx._side is None or Ctx._side.device != self.dev:
@@ -1306,21 +1330,20 @@ class Ctx:
             fused = bool(self.L.mrfa_conv2d_mask_supported(C.byref(p)))
             if not fused:
                 p.mask, p.ldm = None, 0
-        hint = getattr(x.st, "bn_hint", None) if (direct and BN_BWD_IN_DGRAD) else None
+        hint = x.st.bn_hint if (direct and BN_BWD_IN_DGRAD) else None
         if pre is not None and not ups and BN_BWD_IN_DGRAD:
-            hint = pre[2].get("hint")                  # (prebn(): this launch is the only writer of d(relu(bn(x))), the fresh buffer `tgt`)
-        if hint is not None and hint["red"] is None and not relu_in and x.coff == 0 and x.C == x.st.ld and not padded and not cw.dgrad_flat:
+            hint = pre.hint                            # (prebn(): this launch is the only writer of d(relu(bn(x))), the fresh buffer `tgt`)
+        if hint is not None and hint.red is None and not relu_in and x.coff == 0 and x.C == x.st.ld and not padded and not cw.dgrad_flat:
             # x is the output of a BatchNorm + activation whose ONLY consumer is this convolution (bn_act(out_sole=True)): this launch is the only writer
             # of its gradient, so the first phase of that BatchNorm's backward -- the per-channel sums of du and du * xhat -- rides in its epilogue
             # (mrfa_conv_params.bst_*) where the library has it; _bn_bwd then runs phase 2 only.  One launch less per layer on the encoder's backward chains.
-            bx = hint["x"]
-            red = self.f64z(hint["groups"] * hip.STATS_SLOTS * 2 * x.C + 2)
-            p.stats, p.groups = red.data_ptr(), hint["groups"]
-            p.bst_x, p.bst_ldx, p.bst_relu = bx.ptr, bx.ld, int(hint["relu"])
-            p.bst_scale, p.bst_shift = hint["scale"].data_ptr(), hint["shift"].data_ptr()
-            p.bst_mean, p.bst_invstd = hint["mean"].data_ptr(), hint["invstd"].data_ptr()
+            bx, v = hint.x, hint.v
+            red = self.f64z(v.groups * hip.STATS_SLOTS * 2 * x.C + 2)
+            p.stats, p.groups = red.data_ptr(), v.groups
+            p.bst_x, p.bst_ldx, p.bst_relu = bx.ptr, bx.ld, int(hint.relu)
+            p.bst_scale, p.bst_shift, p.bst_mean, p.bst_invstd = v.ptrs()
             if self.L.mrfa_conv2d_bwdstats_supported(C.byref(p)) and self.L.mrfa_conv2d_groups_supported(C.byref(p)):
-                hint["red"] = red
+                hint.red = red
             else:
                 p.stats = p.bst_x = p.bst_scale = p.bst_shift = p.bst_mean = p.bst_invstd = None
                 p.groups = 0
@@ -1332,44 +1355,46 @@ class Ctx:
             return
         cur = tgt            # holds d(pre(ups(x))) as DATA
         if pre is not None:
-            # gradient through relu(scale*x+shift) is handled by the BN closure: it reads pre[2] (stash)
-            pre[2]["dz"] = cur
-            pre[2]["ups"] = ups
+            # gradient through relu(scale*x+shift) is handled by the BN closure (prebn), which finds it here
+            pre.dz, pre.ups = cur, ups
             return
         # ups only
         self._chk(self.L.mrfa_sumpool2_acc(self.s, cur.ptr, cur.ld, x.N, x.H, x.W, x.C, x.gptr, x.ld, 1.0), "sumpool2")
 
     # -- batch norm -------------------------------------------------------------------------------------------
     @staticmethod
-    def _sync_world(bn) -> int:
-        """>1 when `bn` is a SyncBatchNorm (torch.nn.SyncBatchNorm.convert_sync_batchnorm, reference train.py:43) in an
-        initialised process group: batch statistics are then reduced over all ranks (RCCL all-reduce of 2C doubles)."""
-        if isinstance(bn, torch.nn.SyncBatchNorm) and torch.distributed.is_available() and torch.distributed.is_initialized():
-            return torch.distributed.get_world_size()
-        return 1
+    def _in_process_group(bn) -> bool:
+        """`bn` is a SyncBatchNorm (torch.nn.SyncBatchNorm.convert_sync_batchnorm, reference train.py:43) in an initialised process group"""
+        return isinstance(bn, torch.nn.SyncBatchNorm) and torch.distributed.is_available() and torch.distributed.is_initialized()
 
     @staticmethod
-    def _sync_collective(world: int) -> bool:
-        """issue the statistics exchange?  Always with > 1 rank; MRFA_SYNCBN_FORCE_COLLECTIVE=1 also issues it in a one-rank group (a sum over
-        one rank: the identity) so that the captured-collective schedule can be exercised on a single-GPU box"""
-        return world > 1 or (SYNCBN_FORCE and torch.distributed.is_available() and torch.distributed.is_initialized())
+    def _sync_world(bn) -> int:
+        """> 1: the batch statistics of `bn` are reduced over that many ranks (RCCL all-reduce of 2C doubles)"""
+        return torch.distributed.get_world_size() if Ctx._in_process_group(bn) else 1
 
-    def _bn_finalize(self, bn, stats, count):
+    @staticmethod
+    def _exchanges(bn) -> bool:
+        """are the statistics of `bn` exchanged between ranks in a training step?  Always with > 1 rank; MRFA_SYNCBN_FORCE_COLLECTIVE=1 also issues the
+        collectives in a one-rank group (a sum over one rank: the identity) so that the captured-collective schedule can be exercised on a single-GPU box"""
+        return Ctx._in_process_group(bn) and (SYNCBN_FORCE or torch.distributed.get_world_size() > 1)
+
+    def _bn_vectors(self, Cn: int, G: int) -> BnVectors:
+        return BnVectors(self.f32(G * Cn), self.f32(G * Cn), self.f32(G * Cn), self.f32(G * Cn), G)
+
+    def _bn_finalize(self, bn, stats, count) -> BnVectors:
         Cn = bn.num_features
         done = self._fin_done.pop(stats.data_ptr(), None) if stats is not None else None
         if done is not None:                              # finished inside the producing convolution's call (_fin_params)
             assert done[0] is bn and done[1] == count, "fused BatchNorm finalize: another layer / row count than the convolution was told"
-            scale, shift, mean, invstd = done[2:]
             self.nbt[bn] = self.nbt.get(bn, 0) + self.groups
-            return scale, shift, mean, invstd
-        train = self.train
-        G = self.groups if (train and stats is not None) else 1      # statistic groups: [G][C] results, `count` = rows of the whole batch
-        scale, shift, mean, invstd = self.f32(G * Cn), self.f32(G * Cn), self.f32(G * Cn), self.f32(G * Cn)
-        if train and stats is not None:
+            return done[2]
+        G = self.groups if (self.train and stats is not None) else 1      # statistic groups: [G][C] results, `count` = rows of the whole batch
+        v = self._bn_vectors(Cn, G)
+        if self.train and stats is not None:
             world = self._sync_world(bn)
             if stats.data_ptr() in self._synced:          # exchanged by sync_stats() together with the layers beside it
                 count = count * world
-            elif self._sync_collective(world) and isinstance(bn, torch.nn.SyncBatchNorm):
+            elif self._exchanges(bn):
                 # sum / sum-of-squares over every rank's pixels.  Small layers: ALL slots (of all statistic groups: one collective for the source and the
                 # driving pass) are all-reduced in place (<= 128 KB: the collective is latency-bound
                 # there, and nothing but the collective is launched -- round 3 summed, zeroed and copied: three glue launches per layer and direction,
@@ -1382,20 +1407,18 @@ class Ctx:
                 count = count * world
         if G > 1:
             self._chk(self.L.mrfa_bn_finalize_groups(self.s, stats.data_ptr(), count // G, bn.weight.data_ptr(), bn.bias.data_ptr(),
-                                                     bn.running_mean.data_ptr(), bn.running_var.data_ptr(), BN_MOMENTUM, BN_EPS, Cn, G,
-                                                     scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr()), "bn_finalize_groups")
+                                                     bn.running_mean.data_ptr(), bn.running_var.data_ptr(), BN_MOMENTUM, BN_EPS, Cn, G, *v.ptrs()), "bn_finalize_groups")
         else:
             self._chk(self.L.mrfa_bn_finalize(self.s, stats.data_ptr() if stats is not None else None, count, bn.weight.data_ptr(),
                                               bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-                                              BN_MOMENTUM, BN_EPS, Cn, int(train), scale.data_ptr(), shift.data_ptr(),
-                                              mean.data_ptr(), invstd.data_ptr()), "bn_finalize")
-        if train:
+                                              BN_MOMENTUM, BN_EPS, Cn, int(self.train), *v.ptrs()), "bn_finalize")
+        if self.train:
             self.nbt[bn] = self.nbt.get(bn, 0) + G     # num_batches_tracked += 1 per statistic group, batched in flush_forward()
-        return scale, shift, mean, invstd
+        return v
 
     def syncbn_lockstep(self, bn) -> bool:
         """should the caller walk independent SyncBatchNorm layers side by side (all convolutions, sync_stats(), all BatchNorm applications)?"""
-        return bool(SYNCBN_LOCKSTEP and self.train and isinstance(bn, torch.nn.SyncBatchNorm) and self._sync_collective(self._sync_world(bn)))
+        return bool(SYNCBN_LOCKSTEP and self.train and self._exchanges(bn))
 
     def sync_stats(self, items):
         """items = [(bn, stats)] of SyncBatchNorm layers that do not depend on each other, statistics accumulated (conv_bn_raw), not yet applied: ONE
@@ -1404,7 +1427,7 @@ class Ctx:
         data gradient of a member is only read by its convolution's closure, which the caller recorded before any bn_act of the group)."""
         if not items or not self.syncbn_lockstep(items[0][0]):
             return
-        grp = {"left": 0, "pending": [], "red": {}} if self.record else None
+        grp = SyncGroup() if self.record else None
         blocks = []
         for bn, st in items:
             nsl = self.groups * hip.STATS_SLOTS * 2 * bn.num_features
@@ -1413,19 +1436,9 @@ class Ctx:
             blocks.append(st)
             self._synced[st.data_ptr()] = grp
             if grp is not None:
-                grp["left"] += 1
-                grp["red"][st.data_ptr()] = self.f64z(nsl + 2)      # the members' backward sums: carved now, back to back (their closures do not run in a row)
+                grp.left += 1
+                grp.red[st.data_ptr()] = self.f64z(nsl + 2)         # the members' backward sums: carved now, back to back (their closures do not run in a row)
         _syncbn_all_reduce_many(blocks)
-
-    def _bn_group_done(self, grp):
-        """one member of a sync_stats() group has run (or skipped) the first phase of its backward; the last one finishes all of them"""
-        grp["left"] -= 1
-        if grp["left"] > 0 or not grp["pending"]:
-            return
-        _syncbn_all_reduce_many([red for _, red in grp["pending"]])
-        for q, _ in grp["pending"]:
-            self._chk(self.L.mrfa_bn_act_bwd(self.s, C.byref(q)), "bn_act_bwd(2)")
-        grp["pending"] = []
 
     def _allreduce_slot_sums(self, slots: torch.Tensor, G: int, Cn: int) -> torch.Tensor:
         """wide layers under SyncBatchNorm: the [G][STATS_SLOTS][2C] blocks are summed over the slots locally, the [G][2C] sums are all-reduced (a message of
@@ -1467,30 +1480,27 @@ class Ctx:
         """BatchNorm finalize inside the convolution launch that accumulates `stats` (mrfa_conv_params.fin_*): the small-problem kernel's last
         workgroup does it, every other kernel is followed by the finalize launch inside the call -- bn_act() then finds the result here
         instead of launching mrfa_bn_finalize (366 launches per training step on the keypoint encoder's forward chains)."""
-        if not self.train or stats is None:
-            return
-        if isinstance(bn, torch.nn.SyncBatchNorm) and self._sync_collective(self._sync_world(bn)):
-            return                                        # the statistics are exchanged between the convolution and the finalize
+        if not self.train or stats is None or self._exchanges(bn):
+            return                                        # (exchanged: the collective lies between the convolution and the finalize)
         Cn, G = bn.num_features, self.groups
-        scale, shift, mean, invstd = self.f32(G * Cn), self.f32(G * Cn), self.f32(G * Cn), self.f32(G * Cn)
+        v = self._bn_vectors(Cn, G)
         p.fin_gamma, p.fin_beta = bn.weight.data_ptr(), bn.bias.data_ptr()
         p.fin_rmean, p.fin_rvar = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
         p.fin_momentum, p.fin_eps, p.fin_count = BN_MOMENTUM, BN_EPS, count // G
-        p.fin_scale, p.fin_shift, p.fin_mean, p.fin_invstd = scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr()
+        p.fin_scale, p.fin_shift, p.fin_mean, p.fin_invstd = v.ptrs()
         p.fin_counter = stats.data_ptr() + 8 * G * hip.STATS_SLOTS * 2 * Cn
-        self._fin_done[stats.data_ptr()] = (bn, count, scale, shift, mean, invstd)
+        self._fin_done[stats.data_ptr()] = (bn, count, v)
 
     def bn_act(self, x: View, bn, stats, *, relu=True, pool=False, blend=None, out: Optional[View] = None,
                sole_consumer: bool = False, res: Optional[View] = None, out_sole: bool = False) -> View:
         """out = [blend_a*occ +] act(bn(x)) [*(1-occ)], optional 2x2 avg-pool.  x = raw conv output, stats = its
         epilogue-accumulated sums (train) or None (eval)."""
-        scale, shift, mean, invstd = self._bn_finalize(bn, stats, x.rows)
+        v = self._bn_finalize(bn, stats, x.rows)
         Ho, Wo = (x.H // 2, x.W // 2) if pool else (x.H, x.W)
         out = out or self.new(x.N, Ho, Wo, x.C)
         p = hip.BnActParams()
         p.x, p.ldx, p.N, p.H, p.W, p.C = x.ptr, x.ld, x.N, x.H, x.W, x.C
-        p.scale, p.shift, p.relu, p.pool = scale.data_ptr(), shift.data_ptr(), int(relu), int(pool)
-        p.groups = self.groups if (self.train and stats is not None) else 1
+        p.scale, p.shift, p.relu, p.pool, p.groups = v.scale.data_ptr(), v.shift.data_ptr(), int(relu), int(pool), v.groups
         if blend is not None:
             a, occ = blend
             p.blend_a, p.lda, p.occ, p.ldo = a.ptr, a.ld, occ.ptr, occ.ld
@@ -1499,49 +1509,49 @@ class Ctx:
             p.res, p.ldr = res.ptr, res.ld
         p.y, p.ldy = out.ptr, out.ld
         self._chk(self.L.mrfa_bn_act_fwd(self.s, C.byref(p)), "bn_act_fwd")
+        grp = self._synced.pop(stats.data_ptr(), None) if stats is not None else None       # sync_stats(): the backward sums travel together too
         if self.record:
-            train = self.train
             if sole_consumer and x.coff == 0 and x.ld == x.C and x.st.grad is None and not self.in_backward:
                 x.st.grad_noinit = True               # this BN's backward is the only writer of x.grad and covers all of it
 
-            hint = None
-            if (out_sole and train and not pool and blend is None and res is None and out.coff == 0 and out.C == out.st.ld
-                    and not (isinstance(bn, torch.nn.SyncBatchNorm) and self._sync_collective(self._sync_world(bn)))):
-                # the caller states that ONE convolution consumes `out`: its data gradient may carry this BatchNorm's first backward phase (_conv_dgrad)
-                hint = out.st.bn_hint = {"x": x, "scale": scale, "shift": shift, "mean": mean, "invstd": invstd, "relu": relu, "red": None,
-                                         "groups": p.groups}
-
-            groups = p.groups
-            grp = self._synced.pop(stats.data_ptr(), None) if stats is not None else None       # sync_stats(): the backward sums travel together too
-            if grp is not None:
-                grp = (grp, grp["red"].pop(stats.data_ptr()))
+            # the caller states that ONE convolution consumes `out`: its data gradient may carry this BatchNorm's first backward phase (_conv_dgrad)
+            sole = out_sole and not pool and blend is None and res is None and out.coff == 0 and out.C == out.st.ld
+            hint = self._bn_hint(x, bn, v, relu) if sole else None
+            if hint is not None:
+                out.st.bn_hint = hint
+            grp_red = grp.red.pop(stats.data_ptr()) if grp is not None else None
 
             def bwd():
                 if not out.has_grad:
                     if grp is not None:
-                        self._bn_group_done(grp[0])
+                        grp.member_done(self)
                     return
-                self._bn_bwd(x, bn, scale, shift, mean, invstd, relu, pool, out.gptr, out.ld, blend, train, x, res, hint=hint, groups=groups, group=grp)
+                self._bn_bwd(x, bn, v, relu=relu, pool=pool, dy=(out.gptr, out.ld), blend=blend, res=res, hint=hint, group=grp, group_red=grp_red)
             self.tape.append(bwd)
-        elif stats is not None:
-            self._synced.pop(stats.data_ptr(), None)
         return out
 
-    def _bn_bwd(self, x, bn, scale, shift, mean, invstd, relu, pool, dy_ptr, dy_ld, blend, train, dx_view, res=None, hint=None, groups=1, group=None):
+    def _bn_hint(self, x: View, bn, v: BnVectors, relu: bool) -> Optional[BnHint]:
+        """the hint for the one convolution that consumes act(bn(x)); None where no data gradient may carry the first backward phase: in eval mode, and
+        where the sums are exchanged between ranks"""
+        return BnHint(x, v, relu) if self.train and not self._exchanges(bn) else None
+
+    def _bn_bwd(self, x: View, bn, v: BnVectors, *, relu, pool, dy, blend=None, res=None, hint: Optional[BnHint] = None,
+                group: Optional[SyncGroup] = None, group_red=None):
+        """dx, dgamma, dbeta (and d blend / d res) of bn_act / prebn from dy = (pointer, ld).  hint.red: the sums of phase 1, already accumulated by the data
+        gradient that wrote dy; group, group_red: the sync_stats() group the layer belongs to and its block of the group's sums"""
         bg = bngrad(bn)
         if bg not in self.touched_bns:
             self.touched_bns.append(bg)
         dg, db = bg.acc(self.pool32)
-        nred = groups * hip.STATS_SLOTS * 2 * x.C          # (statistic groups: [groups][STATS_SLOTS][2C])
-        pre_red = hint["red"] if hint is not None else None          # the sums of phase 1, already accumulated by the data gradient that wrote dy
-        group, group_red = group if group is not None else (None, None)
+        nred = v.groups * hip.STATS_SLOTS * 2 * x.C          # (statistic groups: [groups][STATS_SLOTS][2C])
+        pre_red = hint.red if hint is not None else None
         # slotted like the statistics buffers (MRFA_STATS_SLOTS) + the fused launch's barrier word
         red = pre_red if pre_red is not None else (group_red if group_red is not None else self.f64z(nred + 2))
         q = hip.BnBwdParams()
         q.x, q.ldx, q.N, q.H, q.W, q.C = x.ptr, x.ld, x.N, x.H, x.W, x.C
-        q.scale, q.shift, q.relu, q.pool = scale.data_ptr(), shift.data_ptr(), int(relu), int(pool)
-        q.mean, q.invstd, q.gamma = mean.data_ptr(), invstd.data_ptr(), bn.weight.data_ptr()
-        q.dy, q.lddy = dy_ptr, dy_ld
+        q.scale, q.shift, q.mean, q.invstd = v.ptrs()
+        q.relu, q.pool, q.gamma = int(relu), int(pool), bn.weight.data_ptr()
+        q.dy, q.lddy = dy
         if blend is not None:
             a, occ = blend
             q.blend_a, q.lda, q.occ, q.ldo = a.ptr, a.ld, occ.ptr, occ.ld
@@ -1549,64 +1559,53 @@ class Ctx:
         if res is not None:
             q.res, q.ldr, q.dres, q.lddr = res.ptr, res.ld, res.gptr, res.ld
         q.red = red.data_ptr()
-        q.dx_overwrite = int(self._claim(dx_view))         # before .gptr, which would zero-fill a fresh buffer
-        q.dx, q.lddx = dx_view.gptr, dx_view.ld
-        q.dgamma, q.dbeta = dg.data_ptr(), db.data_ptr()
-        q.train, q.groups = int(train), groups
-        world = self._sync_world(bn) if train else 1
-        synced = train and self._sync_collective(world) and isinstance(bn, torch.nn.SyncBatchNorm)
+        q.dx_overwrite = int(self._claim(x))               # before .gptr, which would zero-fill a fresh buffer
+        q.dx, q.lddx = x.gptr, x.ld
+        q.dgamma, q.dbeta, q.train, q.groups = dg.data_ptr(), db.data_ptr(), int(self.train), v.groups
         if pre_red is None:
             q.phase = 1
             self._chk(self.L.mrfa_bn_act_bwd(self.s, C.byref(q)), "bn_act_bwd(1)")
         else:
             q.red_all = 1                                   # the convolution's epilogue spread its sums over all slots
-        if synced:
+        q.phase = 2
+        if self.train and self._exchanges(bn):
             # SyncBN backward: the batch means of du and du*xhat are global; gamma/beta gradients stay local sums: taken from the local slots by one
             # launch, then the slots are all-reduced in place and phase 2 divides by world x the local row count (mrfa_bnbwd_params.red_world).
             # (Round 3: sum, two adds, the collective and a division = five launches per layer.)
-            Cn = x.C
-            self._chk(self.L.mrfa_bn_param_grad_groups(self.s, red.data_ptr(), Cn, groups, dg.data_ptr(), db.data_ptr()), "bn_param_grad")
-            q.red_world = world
+            self._chk(self.L.mrfa_bn_param_grad_groups(self.s, red.data_ptr(), x.C, v.groups, dg.data_ptr(), db.data_ptr()), "bn_param_grad")
+            q.red_world = self._sync_world(bn)
             q.dgamma = q.dbeta = None
-            q.phase = 2
-            if group is not None:                           # sync_stats(): the sums of the group's members are exchanged together (_bn_group_done)
-                group["pending"].append((q, red))
-                self._bn_group_done(group)
+            if group is not None:                           # sync_stats(): the sums of the group's members are exchanged together (SyncGroup.member_done)
+                group.pending.append((q, red))
+                group.member_done(self)
                 return
             if nred * 8 <= SYNCBN_DIRECT_BYTES:
                 _syncbn_all_reduce(red[:nred])
             else:
-                q.red = self._allreduce_slot_sums(red, groups, Cn).data_ptr()
+                q.red = self._allreduce_slot_sums(red, v.groups, x.C).data_ptr()
         elif group is not None:
-            self._bn_group_done(group)
-        q.phase = 2
+            group.member_done(self)
         self._chk(self.L.mrfa_bn_act_bwd(self.s, C.byref(q)), "bn_act_bwd(2)")
 
     def prebn(self, x: View, bn, stats=None):
         """Pre-activation BN+ReLU folded into the next conv's prologue (ResBlock2d / ChannelBlock2d).  Returns the `pre`
-        triple for conv(); must be called BEFORE that conv so the tape order is right (its closure runs AFTER the conv's)."""
+        argument of conv(), a Prologue; must be called BEFORE that conv so the tape order is right (its closure runs AFTER the conv's)."""
         assert self.groups == 1 or stats is not None, "pre-activation BatchNorm with statistic groups needs the producing convolution's grouped statistics"
         if self.train and stats is None:
             stats = self.f64z(hip.STATS_SLOTS * 2 * x.C)
             self._chk(self.L.mrfa_bn_stats(self.s, x.ptr, x.ld, x.rows, x.C, stats.data_ptr()), "bn_stats")
-        scale, shift, mean, invstd = self._bn_finalize(bn, stats, x.rows)
-        groups = self.groups if (self.train and stats is not None) else 1
-        stash = {"groups": groups}
+        v = self._bn_finalize(bn, stats, x.rows)
+        # the consuming convolution's data gradient writes d(relu(bn(x))) into a buffer of its own: the first phase of this BatchNorm's backward may
+        # ride in its epilogue (_conv_dgrad), as for bn_act(out_sole=True)
+        pre = Prologue(v.scale.data_ptr(), v.shift.data_ptr(), v.groups, self._bn_hint(x, bn, v, True) if self.record else None, v)
         if self.record:
-            train = self.train
-            if train and not (isinstance(bn, torch.nn.SyncBatchNorm) and self._sync_collective(self._sync_world(bn))):
-                # the consuming convolution's data gradient writes d(relu(bn(x))) into a buffer of its own: the first phase of this BatchNorm's backward may
-                # ride in its epilogue (_conv_dgrad), as for bn_act(out_sole=True)
-                stash["hint"] = {"x": x, "scale": scale, "shift": shift, "mean": mean, "invstd": invstd, "relu": True, "red": None, "groups": groups}
-
             def bwd():
-                dz = stash.get("dz")
-                if dz is None:
+                if pre.dz is None:
                     return
-                assert not stash.get("ups", False)
-                self._bn_bwd(x, bn, scale, shift, mean, invstd, True, False, dz.ptr, dz.ld, None, train, x, hint=stash.get("hint"), groups=groups)
+                assert not pre.ups
+                self._bn_bwd(x, bn, v, relu=True, pool=False, dy=(pre.dz.ptr, pre.dz.ld), hint=pre.hint)
             self.tape.append(bwd)
-        return (scale, shift, stash)
+        return pre
 
     def prologue_ok(self, x: View, conv) -> bool:
         """may the BatchNorm-apply + ReLU between two convolutions of a residual block ride in the second one's prologue (forward, data gradient and weight
@@ -1619,13 +1618,13 @@ class Ctx:
             return False
         if self.groups <= 1:
             return True
-        p = hip.ConvParams()
+        p, pre = hip.ConvParams(), Prologue(x.ptr, x.ptr, self.groups)    # (placeholders of the right alignment for the query; the weights likewise)
         p.x, p.ldx, p.Hin, p.Win, p.N, p.Cin = x.ptr, x.ld, x.H, x.W, x.N, cw.Cin
-        p.in_scale = p.in_shift = p.y = x.ptr                             # (placeholders of the right alignment for the query; the weights likewise)
+        p.in_scale, p.in_shift, p.y = pre.scale, pre.shift, x.ptr
         self._weight_fields(p, cw, "fwd", query=x.ptr)
         p.in_relu, p.ldy, p.Cout, p.Hout, p.Wout = 1, _r4(cw.Cout), cw.Cout, x.H + 2 * cw.pad - cw.R + 1, x.W + 2 * cw.pad - cw.S + 1
         p.R, p.S, p.pad, p.alpha, p.nbatch, p.groups = cw.R, cw.S, cw.pad, 1.0, 1, self.groups
-        q = self._wgrad_params(x, cw, x.ptr, _r4(cw.Cout), p.Hout, p.Wout, x.ptr, pre=(x.ptr, x.ptr, self.groups))
+        q = self._wgrad_params(x, cw, x.ptr, _r4(cw.Cout), p.Hout, p.Wout, x.ptr, pre=pre)
         return bool(self.L.mrfa_conv2d_groups_supported(C.byref(p)) and self.L.mrfa_conv2d_wgrad_groups_supported(C.byref(q)))
 
     # -- samplers ---------------------------------------------------------------------------------------------
@@ -2452,7 +2451,7 @@ class Ctx:
                 fp = float(arena.abs().sum(dtype=torch.float64)) if total else 0.0
                 rec.append((i, desc, fp))
             dbg.append(rec)
-        if getattr(self, "side_used", False):         # join the weight-gradient side chain before anyone reads dW
+        if self.side_used:                            # join the weight-gradient side chain before anyone reads dW
             torch.cuda.current_stream(self.dev).wait_stream(Ctx._side)
             self.side_used = False
         self.tape = []

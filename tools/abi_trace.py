@@ -161,11 +161,14 @@ def programs(lines):
         if direct:
             FlatGradients(rf.parameters()).bind()
 
-        def step(tag):
+        def step(tag, deferred=None):
             leaves = [t.clone().requires_grad_(True) for t in (kp_s, kp_d, dmo["deformation"], dmo["occlusion"])]
-            with (engine.direct_param_grads() if direct else contextlib.nullcontext()):
+            with (engine.direct_param_grads() if direct else contextlib.nullcontext()), engine.defer_wgrads(deferred):
                 o, _, _ = rf(leaves[0], leaves[1], {"deformation": leaves[2], "occlusion": leaves[3]}, img, img_full)
                 (o - driving).abs().mean().backward()
+            if deferred is not None:                 # the weight gradients and their un-packing into .grad are issued by the join
+                deferred.join(torch.device("cpu"))
+                deferred.reset()
             _result(lines, tag, [o] + [t.grad for t in leaves], rf)
         step("raft/1")
         plan = engine.PackPlan(rf)
@@ -175,6 +178,10 @@ def programs(lines):
                 p.mul_(0.75)
         plan.run()
         step("raft/2")
+        if direct:                                   # the same step with its weight gradients deferred: one launch each, then one parameter array
+            for batch in (False, True):
+                lines.append(f"# program raft deferred batch={batch}")
+                step(f"raft/deferred{int(batch)}", engine.DeferredWgrads(batch=batch))
 
     lines.append("# program small_hrnet stat_groups(2)")
     m = small_hrnet()
@@ -183,6 +190,8 @@ def programs(lines):
         y = m(det_uniform("sbh/x", (4, 3, 32, 32)))
     (y * det_uniform("sbh/w", (4, 32, 8, 8))).sum().div(4.0).backward()
     _result(lines, "hrnet", [y], m)
+
+    _syncbn_programs(lines)
 
     lines.append("# program prior stage")
     x = cases.images("g11/x_train", 2, 256)
@@ -198,6 +207,39 @@ def programs(lines):
     r = dmm(x, cases.keypoints("g11/kd_train", 2), cases.keypoints("g11/ks_train", 2))
     ((r["deformation"].sum() + r["occlusion"].sum() + r["mask"].square().sum()) / 64.0).backward()
     _result(lines, "dm", [r["deformation"], r["occlusion"], r["mask"]], dmm)
+
+
+def _syncbn_programs(lines):
+    """small_hrnet() under SyncBatchNorm in a one-rank gloo group with the collectives forced (a sum over one rank): depth-batched collectives, one per
+    layer and direction, and every layer on the wide-layer path (slot sums first).  Each collective is a trace line of its own."""
+    import tempfile
+    import torch.distributed as dist
+    from mrfa_amd import engine
+    from mrfa_amd.utils.prng import det_uniform
+    from tests.test_wiring_cpu import small_hrnet
+
+    saved = engine.SYNCBN_FORCE, engine.SYNCBN_LOCKSTEP, engine.SYNCBN_DIRECT_BYTES, engine._syncbn_all_reduce
+    reduce_ = engine._syncbn_all_reduce
+
+    def traced_reduce(t, layers=1):
+        lines.append(f"collective numel={t.numel()} layers={layers}")
+        return reduce_(t, layers)
+    with tempfile.TemporaryDirectory() as tmp:
+        dist.init_process_group("gloo", init_method="file://" + os.path.join(tmp, "store"), rank=0, world_size=1)
+        try:
+            engine.SYNCBN_FORCE, engine._syncbn_all_reduce = True, traced_reduce
+            for lockstep, direct_bytes, groups in ((True, saved[2], 1), (False, saved[2], 1), (True, 0, 2)):
+                lines.append(f"# program small_hrnet SyncBatchNorm lockstep={lockstep} direct_bytes={direct_bytes} stat_groups({groups})")
+                engine.SYNCBN_LOCKSTEP, engine.SYNCBN_DIRECT_BYTES = lockstep, direct_bytes
+                m = torch.nn.SyncBatchNorm.convert_sync_batchnorm(small_hrnet())
+                m.train(True)
+                with engine.stat_groups(groups):
+                    y = m(det_uniform("sbh/x", (4, 3, 32, 32)))
+                (y * det_uniform("sbh/w", (4, 32, 8, 8))).sum().div(4.0).backward()
+                _result(lines, f"syncbn/{int(lockstep)}/{direct_bytes}/{groups}", [y], m)
+        finally:
+            engine.SYNCBN_FORCE, engine.SYNCBN_LOCKSTEP, engine.SYNCBN_DIRECT_BYTES, engine._syncbn_all_reduce = saved
+            dist.destroy_process_group()
 
 
 def main(out_path):
