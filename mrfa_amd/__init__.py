@@ -32,3 +32,12 @@ def graph_replay_safe(what: str = "hipGraph capture") -> None:
 
 
 __version__ = "0.2.0"
+
+_AUGMENT_EXPORTS = ("PairAugmenter", "PairParams", "PairDraw")      # mrfa_amd/augment.py, imported on first use (it imports torch)
+
+
+def __getattr__(name):
+    if name in _AUGMENT_EXPORTS:
+        from . import augment
+        return getattr(augment, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
