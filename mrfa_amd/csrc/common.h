@@ -10,14 +10,13 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 void mrfa_set_error(const char* fmt, ...);
 
-// conv_plan.hip: the dispatch switches, one table (mrfa_set_tuning keys; the MRFA_* environment variables seed them once, at load)
+// conv_plan.hip: the dispatch switches, one table (every field is a mrfa_set_tuning key; the library reads no environment)
 struct MrfaTuning {
-    int conv_small_env;                    // MRFA_CONV_SMALL (no key: conv_small below is the runtime switch, both must be on)
     int conv_small;
     int conv_halo, conv_halo_min_tiles, conv_halo_pr, conv_halo_phase, conv_halo_bn256, conv_halo_bn192, conv_halo_bn64_fill;
     int conv_lean, conv_lean_min_wgs, conv_lean_geo, gemm_lean;
     int wgrad_halo, wgrad_halo_min_wgs, wgrad_halo_target_wgs, wgrad_halo_phase, wgrad_lean;
-    int conv_fewout3, attention_mfma, split_target_256;
+    int conv_fewout3, attention_mfma;
 };
 extern MrfaTuning g_tune;
 

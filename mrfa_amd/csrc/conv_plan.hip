@@ -4,22 +4,16 @@
 // answer for it.  The dispatchers launch what the plan says and every query reads the same plan, so a query cannot drift from its launch.
 #include "common.h"
 #include <stdarg.h>
-#include <stdlib.h>
-
-namespace {
-int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-int env_on(const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); }
-}  // namespace
 
 MrfaTuning g_tune = {
-    /*conv_small_env*/ env_on("MRFA_CONV_SMALL"), /*conv_small*/ 1,
-    /*conv_halo*/ env_on("MRFA_CONV_HALO"), /*conv_halo_min_tiles*/ 128, /*conv_halo_pr*/ 0, /*conv_halo_phase*/ 1, /*conv_halo_bn256*/ 1,
+    /*conv_small*/ 1,
+    /*conv_halo*/ 1, /*conv_halo_min_tiles*/ 128, /*conv_halo_pr*/ 0, /*conv_halo_phase*/ 1, /*conv_halo_bn256*/ 1,
     /*conv_halo_bn192*/ 1, /*conv_halo_bn64_fill*/ 1,
-    /*conv_lean*/ env_on("MRFA_CONV_LEAN"), /*conv_lean_min_wgs*/ 128, /*conv_lean_geo*/ -1,
-    /*gemm_lean*/ env_int("MRFA_GEMM_LEAN", 1),      // 0 off, 1 where measured faster, 2 wherever it can run
-    /*wgrad_halo*/ env_on("MRFA_WGRAD_HALO"), /*wgrad_halo_min_wgs*/ 192, /*wgrad_halo_target_wgs*/ 256, /*wgrad_halo_phase*/ 1,
-    /*wgrad_lean*/ env_on("MRFA_WGRAD_LEAN"),
-    /*conv_fewout3*/ 1, /*attention_mfma*/ env_on("MRFA_ATTENTION_MFMA"), /*split_target_256*/ env_int("MRFA_SPLIT_TARGET_256", 1),
+    /*conv_lean*/ 1, /*conv_lean_min_wgs*/ 128, /*conv_lean_geo*/ -1,
+    /*gemm_lean*/ 1,      // 0 off, 1 where measured faster, 2 wherever it can run
+    /*wgrad_halo*/ 1, /*wgrad_halo_min_wgs*/ 192, /*wgrad_halo_target_wgs*/ 256, /*wgrad_halo_phase*/ 1,
+    /*wgrad_lean*/ 1,
+    /*conv_fewout3*/ 1, /*attention_mfma*/ 1,
 };
 
 // how mrfa_set_tuning stores a value: on / off, as given, only when >= 0 (as given / as on-off / at most 2), only when > 0
@@ -123,7 +117,7 @@ void plan_rows(ConvPlan& c, const mrfa_conv_params& p, int mode) {
             // units in one burst behind the k-loop (12 + 6 us of a 51 us launch, profiles/r6_splitk_launch_timeline.txt), and with the 128-row tile kept half the
             // slices are 5-6 us faster on 8 <= t <= 16 tiles (tools/sweep_splitk.py TILE128=1 COLD=1 FUSED=1: 1024 -> 1024 @4^2 52.3 -> 47.1, 512 -> 512 @8^2
             // 51.4 -> 46.7, 1024 -> 256 @8^2 up 53.0 -> 46.5, 256 -> 512 @8^2 42.8 -> 36.0)
-            const bool half_target = g_tune.split_target_256 && auto_split && p.sk_ticket && !p.accumulate && KT >= 72 && KT <= 320 && BM == 128 && t >= 8 && t <= 16;      // (deeper K: 2048 -> 512 @8^2 up wants its 32 slices, 86 against 101 us)
+            const bool half_target = auto_split && p.sk_ticket && !p.accumulate && KT >= 72 && KT <= 320 && BM == 128 && t >= 8 && t <= 16;      // (deeper K: 2048 -> 512 @8^2 up wants its 32 slices, 86 against 101 us)
             int want = (int)(((half_target ? 256 : 512) + t - 1) / t);
             if (auto_split) splitk = want <= max_split ? want : max_split;
             const int min_bm = (BN == 128) ? 32 : (BN == 64 ? 64 : 128);
@@ -175,7 +169,7 @@ ConvPlan plan_conv(const mrfa_conv_params& p) {
     c.lean_geo = flat ? -1 : mrfa_conv_lean_pick(p);
     c.gemm_cfg = (flat || c.lean_geo >= 0) ? -1 : mrfa_gemm_lean_pick(p, c.M);
     const bool lean = c.lean_geo >= 0, gemm = c.gemm_cfg >= 0;
-    const bool small = !lean && !gemm && g_tune.conv_small_env && g_tune.conv_small && mrfa_conv_small_eligible(p, c.M);
+    const bool small = !lean && !gemm && g_tune.conv_small && mrfa_conv_small_eligible(p, c.M);
     const bool halo = !flat && mrfa_conv_halo_eligible(p, &c.halo);
 
     // the capability queries (mrfa_hip.h)
@@ -253,7 +247,7 @@ WgradPlan plan_wgrad(const mrfa_wgrad_params& p) {
     const bool flat = p.kflat > 0;
     c.M = (long long)p.N * p.Hout * p.Wout;
     c.lean = mrfa_wgrad_lean_eligible(p);
-    c.small = g_tune.conv_small_env && g_tune.conv_small && mrfa_wgrad_small_eligible(p, c.M);
+    c.small = g_tune.conv_small && mrfa_wgrad_small_eligible(p, c.M);
     c.groups_ok = p.groups <= 1 || !p.in_scale || c.lean;
     c.stride2_ok = p.stride == 2 && p.Hout == (p.Hin + 2 * p.pad - p.R) / 2 + 1 && p.Wout == (p.Win + 2 * p.pad - p.S) / 2 + 1 && c.small;
     if (!(p.x && p.dy && p.dw)) return refuse(c, "wgrad: null pointer");

@@ -265,36 +265,24 @@ def _syncbn_all_reduce_many(ts):
             runs.append([base, lo, hi, 1])
     for base, lo, hi, n in runs:
         _syncbn_all_reduce(base.view(-1)[lo:min(hi, base.numel())], n)
-SYNCBN_DIRECT_BYTES = int(os.environ.get("MRFA_SYNCBN_DIRECT_KIB", "128")) << 10      # statistics blocks up to this size are all-reduced whole (all slots)
-PHASE_UPCONV = os.environ.get("MRFA_PHASE_UPCONV", "1") != "0"        # forward / data gradient of fused-upsample 3x3 layers in phase form
-# BatchNorm finalize of the conv -> BatchNorm pairs of the keypoint encoder inside the convolution's launch (last workgroup; mrfa_conv_params.fin_*)
-BN_FIN_FUSED = os.environ.get("MRFA_BN_FIN_FUSED", "1") != "0"
-# first phase of the BatchNorm backward of single-consumer BatchNorm outputs inside the consumer's data-gradient launch (mrfa_conv_params.bst_*)
-BN_BWD_IN_DGRAD = os.environ.get("MRFA_BN_BWD_IN_DGRAD", "1") != "0"
-FUSED_RESIZES = os.environ.get("MRFA_FUSED_RESIZES", "1") != "0"      # copies / resizes issued inside Ctx.fused_resizes() travel as ONE launch per direction (kept for same-box A/B runs)
-FUSED_SPLITK = os.environ.get("MRFA_FUSED_SPLITK", "1") != "0"        # K splits that finish inside their launch (Ctx._conv_out; kept for same-box A/B runs)
+SYNCBN_DIRECT_BYTES = 128 << 10      # statistics blocks up to this size are all-reduced whole (all slots)
 # BatchNorm-apply + ReLU between the two convolutions of a residual block as the second one's prologue (Ctx.prologue_ok; hr_base.BasicBlock): 56 launches and
 # 56 x 8 MB tensors fewer per forward pass, exact (tests/test_graph_gpu.py::test_prologue_fusion_equals_the_bn_act_path) -- and measured SLOWER in the
 # training step: 81.61 ms (81.4-81.8) against 80.30 (79.5-80.9) without it over three alternating rounds of 40 steps on one box
 # (profiles/r6_ab_prologue_wgrad_lean.txt): the split + prologue arithmetic lands in the staging of conv_lean / wgrad_lean, whose one or two waves per SIMD
 # have no slack for it, while the bn_act launches it removes ran beside other lanes' kernels.  OFF by default (MRFA_PROLOGUE_FUSION=1 switches it on).
 PROLOGUE_FUSION = os.environ.get("MRFA_PROLOGUE_FUSION", "0") == "1"
-LAZY_FP32_PACKS = os.environ.get("MRFA_LAZY_FP32_PACKS", "1") != "0"      # fp32 weight layouts only for the launches that read them (Ctx._fp32_weights)
-RELU_IN = os.environ.get("MRFA_RELU_IN", "1") != "0"                  # ReLU backward of single-consumer tensors inside the consumer's data gradient
 # gradient buffers of at least this many floats are not zero-filled before the backward pass (Storage.fresh); smaller ones share one
-# zero arena (one fill instead of hundreds of tiny ones).  9 MiB (round 2: 4): the TokenPose_B encoder's 4 and 8 MiB buffers (32 / 64
-# channels @64^2, B = 8) are mostly first touched by accumulating kernels (residual gradients, sub-sampling, GELU, attention), i.e. each
-# paid its own fill launch on a latency-bound chain -- 259 fill launches per step; A/B on one box 89.2 -> 88.5 ms.
-FRESH_MIN_ELEMS = (int(os.environ.get("MRFA_FRESH_MIN_MIB", "9")) << 20) // 4
-# debug switch (MRFA_FRESH_NAN=1; tests set it together with FRESH_MIN_ELEMS = 0): every lazily initialised gradient buffer starts
+# zero arena (one fill instead of hundreds of tiny ones).  9 MiB keeps the TokenPose_B encoder's 4 and 8 MiB buffers, which accumulating
+# kernels touch first, in the arena (measured: DESIGN 3h).
+FRESH_MIN_ELEMS = (9 << 20) // 4
+# debug switch (tests set it together with FRESH_MIN_ELEMS = 0): every lazily initialised gradient buffer starts
 # as NaN instead of whatever the allocator hands out, so a kernel that READS a buffer no writer has covered -- or a first writer that
 # does not cover all of it -- shows up as a non-finite gradient instead of passing by luck
-FRESH_NAN = os.environ.get("MRFA_FRESH_NAN", "0") == "1"
-# HRNet's resolution branches (three independent chains of BasicBlocks per stage-3 module) as parallel branches of the captured hipGraph (Ctx.lanes()).
-# On since round 5: with ONE batched encoder pass (statistic groups below) the forward chain takes 8.2 instead of 10.3 ms with them (round 4, beside a
-# second encoder pass on its own stream, they lost: more than four live branches are folded together by the graph executor).  Never with
-# SyncBatchNorm collectives (every rank must enqueue them on ONE stream in ONE order): mrfa_amd.graph.GraphedTrainStep switches them off then.
-BRANCH_STREAMS = os.environ.get("MRFA_BRANCH_STREAMS", "1") != "0"        # (kept as a switch for same-box A/B runs)
+FRESH_NAN = False
+# HRNet's resolution branches (three independent chains of BasicBlocks per stage-3 module) as parallel branches of the captured hipGraph (Ctx.lanes(),
+# DESIGN 3e).  Never with SyncBatchNorm collectives (every rank must enqueue them on ONE stream in ONE order): mrfa_amd.graph.GraphedTrainStep clears it then.
+BRANCH_STREAMS = True
 
 
 # ---- statistic groups (include/mrfa_hip.h v7): the reference's separate encoder calls -- encoder(source), encoder(driving), encoder(transformed driving),
@@ -1066,7 +1054,7 @@ class Ctx:
         relu_in: the caller states that x (all of its storage) holds ReLU outputs and that this conv is their only consumer: the ReLU
         backward of x's producers then rides in this conv's data gradient (mrfa_conv_params.mask) instead of a pass of its own."""
         cw = convw(conv)
-        relu_in = bool(relu_in and RELU_IN and self.record and need_dx and pre is None and not ups)
+        relu_in = bool(relu_in and self.record and need_dx and pre is None and not ups)
         if relu_in:
             assert x.coff == 0 and x.C == x.st.ld, "relu_in: the view must cover its storage (every producer skips its ReLU backward)"
             x.st.bwd_masked = True
@@ -1106,7 +1094,7 @@ class Ctx:
         p.x, p.ldx, p.Hin, p.Win, p.ups, p.N, p.Cin = x.ptr, x.ld, x.H, x.W, int(ups), x.N, cw.Cin
         padded = cw.fwd_flat and x.zpad and x.coff % 4 == 0 and pre is None
         fp32 = self._weight_fields(p, cw, "fwd", padded)
-        if self.split and not cw.fwd_flat and ups and cw.R == 3 and cw.S == 3 and cw.pad == 1 and PHASE_UPCONV:
+        if self.split and not cw.fwd_flat and ups and cw.R == 3 and cw.S == 3 and cw.pad == 1:
             # UpBlock2d: the library may run nearest-x2 + 3x3 as four 2x2 phase convolutions (16 / 36 of the MACs, csrc/conv_halo.hip)
             wph = cw.layout("fwd_phase")
             p.w_phase, p.w_phase_piece = wph.data_ptr(), wph.numel() // 3
@@ -1202,7 +1190,7 @@ class Ctx:
         ph = p.w_split or p.w_phase
         if not ph or p.w != ph:
             return                                    # (no pre-split planes: conv() / _conv_dgrad() put the fp32 layout there already)
-        if not (LAZY_FP32_PACKS and not self.L.mrfa_conv2d_reads_fp32_weights(C.byref(p))):
+        if self.L.mrfa_conv2d_reads_fp32_weights(C.byref(p)):
             p.w = pack().data_ptr()
 
     def _conv_out(self, p, out: Optional[View], N, Ho, Wo, Cout) -> View:
@@ -1211,7 +1199,7 @@ class Ctx:
         itself come from the zero-filled arena, so that neither the y = bias pass before nor the affine / residual / ReLU / statistics pass behind such a launch
         exists (107 launches per training step on the serial low-resolution chains of the hourglasses and the generator's bottleneck)."""
         rows = N * Ho * Wo
-        if FUSED_SPLITK and rows <= 32768:
+        if rows <= 32768:
             p.sk_ticket = p.x                         # (placeholder for the query, which only asks whether tickets will be there: ADVICE r5 -- the ticket
             if self.L.mrfa_conv2d_split_k(C.byref(p)) > 1:      # block is carved from the zero arena only for launches that do split)
                 p.sk_ticket = self.pool32.take(((rows + 31) // 32) * ((Cout + 31) // 32)).data_ptr()
@@ -1290,7 +1278,7 @@ class Ctx:
                                                     x.gptr, x.ld, cw.Cin, cw.R, cw.pad, 0 if first else 1,
                                                     x.ptr if relu_in else None, x.ld), "conv_fewout_dgrad")
             return
-        if (ups and pre is None and self.split and PHASE_UPCONV and cw.R == 3 and cw.S == 3 and cw.pad == 1 and not cw.dgrad_flat
+        if (ups and pre is None and self.split and cw.R == 3 and cw.S == 3 and cw.pad == 1 and not cw.dgrad_flat
                 and x.coff % 4 == 0):
             # UpBlock2d: data gradient in phase form (four transposed 2x2 convolutions of the phase images of dY, csrc/conv_halo.hip MODE 2)
             # straight into x.grad -- instead of the 3x3 data gradient on the 2H x 2W grid + the 2x2 sum-pooling pass
@@ -1330,8 +1318,8 @@ class Ctx:
             fused = bool(self.L.mrfa_conv2d_mask_supported(C.byref(p)))
             if not fused:
                 p.mask, p.ldm = None, 0
-        hint = x.st.bn_hint if (direct and BN_BWD_IN_DGRAD) else None
-        if pre is not None and not ups and BN_BWD_IN_DGRAD:
+        hint = x.st.bn_hint if direct else None
+        if pre is not None and not ups:
             hint = pre.hint                            # (prebn(): this launch is the only writer of d(relu(bn(x))), the fresh buffer `tgt`)
         if hint is not None and hint.red is None and not relu_in and x.coff == 0 and x.C == x.st.ld and not padded and not cw.dgrad_flat:
             # x is the output of a BatchNorm + activation whose ONLY consumer is this convolution (bn_act(out_sole=True)): this launch is the only writer
@@ -1470,11 +1458,6 @@ class Ctx:
         for g in range(G):
             self._chk(self.L.mrfa_bn_stats(self.s, x.ptr + 4 * g * rows * x.ld, x.ld, rows, x.C, stats.data_ptr() + 8 * g * hip.STATS_SLOTS * 2 * x.C),
                       "bn_stats")
-
-    @staticmethod
-    def fin(bn):
-        """the `fin=` argument of conv() for a convolution whose statistics `bn` consumes (None: the finalize stays a launch of its own)"""
-        return bn if BN_FIN_FUSED else None
 
     def _fin_params(self, p, bn, stats, count: int):
         """BatchNorm finalize inside the convolution launch that accumulates `stats` (mrfa_conv_params.fin_*): the small-problem kernel's last
@@ -1676,7 +1659,7 @@ class Ctx:
         in call order: the arithmetic of the separate launches), and their backward passes as ONE launch grouped by input (down-sampling terms keep
         their scatter launches).  RaftFlow's running-flow updates and its flow / occlusion re-composition between two refinement levels (raft.py:258-262,
         276-295) are ~16 launches over 1- and 2-channel maps per level on a chain where nothing else runs."""
-        if not FUSED_RESIZES or self._rs is not None:
+        if self._rs is not None:
             yield
             return
         self._rs = []
@@ -2175,13 +2158,12 @@ class Ctx:
     def conv_bn_raw(self, x: View, conv, bn, need_dx=True, pre=None):
         """raw = conv(pre(x)) for a conv of stride 1 or 2 that a BatchNorm follows -> (raw, batch statistics of raw); pre: see prebn() / prologue_ok()"""
         cw = convw(conv)
-        fin = bn if BN_FIN_FUSED else None
         if cw.stride == 1:
             st = self.bn_stats_buf(bn)
-            return self.conv(x, conv, stats=st, need_dx=need_dx, fin=fin, pre=pre), st
+            return self.conv(x, conv, stats=st, need_dx=need_dx, fin=bn, pre=pre), st
         assert pre is None
         if cw.stride == 2 and conv.bias is None:
-            got = self._conv_strided(x, conv, cw, self.bn_stats_buf(bn), need_dx, fin=fin)
+            got = self._conv_strided(x, conv, cw, self.bn_stats_buf(bn), need_dx, fin=bn)
             if got is not None:
                 return got
         raw = self.subsample(self.conv(x, conv, need_dx=need_dx), cw.stride)

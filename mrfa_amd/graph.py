@@ -215,7 +215,7 @@ class GraphedTrainStep:
         # Measured (same box, 20 steps): 108.6 vs 111.2 ms.  (Giving the capture / encoder streams high priority on top of it made the
         # replay 1.7x SLOWER -- 182 ms -- so stream priorities are left alone.)
         if defer_wgrads is None:
-            defer_wgrads = (getattr(model, "prior", "") == "mtia" and os.environ.get("MRFA_DEFER_WGRADS", "1") == "1")
+            defer_wgrads = getattr(model, "prior", "") == "mtia"
         if hasattr(model, "defer_decoder_wgrads"):
             model.defer_decoder_wgrads = bool(defer_wgrads) and self.split is None and getattr(optimizer, "fused_clip", False)
         self.src, self.drv = source.clone(), driving.clone()
@@ -248,7 +248,7 @@ class GraphedTrainStep:
         # stream beside the encoder's forward chain, whose small kernels leave the HBM idle (HotPath.await_packs() joins it before the first other use)
         enc = getattr(model, "encoder", None)
         self.pack_stream = None
-        if enc is not None and hasattr(model, "await_packs") and os.environ.get("MRFA_PACK_STREAM", "1") != "0":
+        if enc is not None and hasattr(model, "await_packs"):
             self.packs = engine.PackPlan(model, only=enc)
             self.packs_rest = engine.PackPlan(model, exclude=enc)
             self.pack_stream = torch.cuda.Stream(device=dev)

@@ -6,6 +6,7 @@ the allocator / stream owner here.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -297,6 +298,25 @@ def set_mfma_mode(mode: str):
 def mfma_mode() -> str:
     m = lib().mrfa_get_mfma_mode()
     return next(k for k, v in MFMA_MODES.items() if v == m)
+
+
+@contextlib.contextmanager
+def tuned(*handle, **keys):
+    """with tuned(conv_halo=0, ...): the kernel-selection keys of mrfa_set_tuning (include/mrfa_hip.h) hold these values inside and what they held before
+    afterwards, also when the body raises.  tuned(L, ...) drives a library the caller loaded itself.  A key the library does not know raises KeyError
+    before the body runs, with every key as it was (mrfa_set_tuning answers -1 for one; only conv_lean_geo stores -1 itself)."""
+    (L,) = handle or (lib(),)
+    prev = []
+    try:
+        for key, value in keys.items():
+            was = L.mrfa_set_tuning(key.encode(), int(value))
+            if was == -1 and key != "conv_lean_geo":
+                raise KeyError(key)
+            prev.append((key, was))
+        yield
+    finally:
+        for key, was in reversed(prev):
+            L.mrfa_set_tuning(key.encode(), was)
 
 
 def check(rc: int, what: str):

@@ -9,7 +9,6 @@ from __future__ import annotations
 
 import contextlib
 import math
-import os
 
 import torch
 from torch import nn
@@ -84,13 +83,11 @@ class HotPath(nn.Module):
         from .engine import DeferredWgrads
         object.__setattr__(self, "_wdefer", DeferredWgrads())
         object.__setattr__(self, "_wdefer_dev", None)
-        # the keypoint encoder's own weight gradients (~200 small launches inside its backward chain): collected and dealt onto
-        # MRFA_ENC_WGRAD_FANOUT (default 4; 0 / 1 = in line) side streams after the chain: the backward chain loses a fifth of
-        # its launches, the independent launches then run four abreast as multi-problem launches (round 3, 5 alternating runs of 20 steps on one box:
-        # 85.9 -> 84.2 ms).  Same conditions as defer_decoder_wgrads.
+        # the keypoint encoder's own weight gradients (~200 small launches inside its backward chain): collected and dealt onto four side streams
+        # after the chain: the backward chain loses a fifth of its launches, the independent launches then run four abreast as multi-problem
+        # launches.  Same conditions as defer_decoder_wgrads.
         self.defer_encoder_wgrads = True       # (GraphedTrainStep switches it off with SyncBatchNorm: one stream, one enqueue order per rank)
-        object.__setattr__(self, "_wdefer_enc", DeferredWgrads(fanout=int(os.environ.get("MRFA_ENC_WGRAD_FANOUT", "4") or 0), manual=True,
-                                                                   batch=True))
+        object.__setattr__(self, "_wdefer_enc", DeferredWgrads(fanout=4, manual=True, batch=True))
         # test / diagnostics hook: a dict here makes forward() keep the keypoint tensors (`kp_s`, `jac_s`, `kp_d`, `jac_d`) and copy the
         # gradients that arrive at them into static buffers (`dkp_s`, ...) with a kernel (no memcpy node), so that d loss / d keypoints of
         # a hipGraph-REPLAYED step can be read (tests/test_headline_gpu.py).  None (default): nothing is recorded

@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from mrfa_amd.hip import ConvParams, WgradParams
+from mrfa_amd.hip import ConvParams, WgradParams, tuned
 
 BASE = 1 << 32          # tools/conv_plan_table.py: pointer field i of a block sits at BASE + i * 4 KiB + its stored offset
 
@@ -46,16 +46,12 @@ def _answers(L, t, kind, struct):
     got = np.zeros_like(t[f"{kind}_answers"])
     for ti, tuning in enumerate(str(s) for s in t["tunings"]):
         key, _, value = tuning.partition("=")
-        prev = L.mrfa_set_tuning(key.encode(), int(value)) if key else None
-        try:
+        with tuned(L, **({key: int(value)} if key else {})):
             for mode in range(4):
                 assert L.mrfa_set_mfma_mode(mode) == 0
                 for i in np.nonzero((t[f"{kind}_tuning"] == ti) & (t[f"{kind}_mode"] == mode))[0]:
                     p = _block(struct, ptr_names, t[f"{kind}_ptrs"][i], val_names, t[f"{kind}_vals"][i])
                     got[i] = [f(C.byref(p)) for f in fns]
-        finally:
-            if key:
-                L.mrfa_set_tuning(key.encode(), prev)
     return queries, got
 
 
@@ -79,3 +75,78 @@ def test_wgrad_queries_match_the_table(lib, table):
     assert drift.any()
     want[drift, queries.index("wgrad_stride_supported")] = 0
     assert not _mismatches(table, "wgrad", queries, got, want)
+
+
+# ---- hip.tuned: the one way to flip a mrfa_set_tuning key and put it back
+KEYS = ["conv_small", "conv_halo", "conv_halo_min_tiles", "conv_halo_pr", "conv_halo_phase", "conv_halo_bn256", "conv_halo_bn192", "conv_halo_bn64_fill",
+        "conv_lean", "conv_lean_min_wgs", "conv_lean_geo", "gemm_lean", "wgrad_halo", "wgrad_halo_min_wgs", "wgrad_halo_target_wgs", "wgrad_halo_phase",
+        "wgrad_lean", "conv_fewout3", "attention_mfma"]
+
+
+def _state(L):
+    """every key's stored value (a key is read by setting it and putting back what the call returned)"""
+    out = {}
+    for k in KEYS:
+        out[k] = L.mrfa_set_tuning(k.encode(), 0)
+        L.mrfa_set_tuning(k.encode(), out[k])
+    return out
+
+
+def test_tuning_defaults_are_constants(lib):
+    s = _state(lib)
+    assert s == {**{k: 1 for k in KEYS}, "conv_halo_min_tiles": 128, "conv_halo_pr": 0, "conv_lean_min_wgs": 128, "conv_lean_geo": -1,
+                 "wgrad_halo_min_wgs": 192, "wgrad_halo_target_wgs": 256}
+
+
+def test_tuned_restores_the_previous_values_after_the_body_raises(lib):
+    before = _state(lib)
+    lib.mrfa_set_tuning(b"conv_halo_min_tiles", 77)           # (not the default: what is restored is what was there)
+    try:
+        with pytest.raises(ZeroDivisionError):
+            with tuned(lib, conv_halo_min_tiles=3, conv_small=0, gemm_lean=2):
+                assert _state(lib) == {**before, "conv_halo_min_tiles": 3, "conv_small": 0, "gemm_lean": 2}
+                1 / 0
+        assert _state(lib) == {**before, "conv_halo_min_tiles": 77}
+    finally:
+        lib.mrfa_set_tuning(b"conv_halo_min_tiles", before["conv_halo_min_tiles"])
+
+
+def test_nested_tuned_blocks_unwind_in_order(lib):
+    before = _state(lib)
+    with tuned(lib, wgrad_halo_min_wgs=1, wgrad_halo=0):
+        with tuned(lib, wgrad_halo_min_wgs=5, wgrad_halo_phase=0):
+            assert _state(lib) == {**before, "wgrad_halo_min_wgs": 5, "wgrad_halo": 0, "wgrad_halo_phase": 0}
+        assert _state(lib) == {**before, "wgrad_halo_min_wgs": 1, "wgrad_halo": 0}
+        with tuned(lib, wgrad_halo_min_wgs=9):                # a second block on a key the outer one holds
+            assert _state(lib)["wgrad_halo_min_wgs"] == 9
+        assert _state(lib) == {**before, "wgrad_halo_min_wgs": 1, "wgrad_halo": 0}
+    assert _state(lib) == before
+
+
+def test_tuned_refuses_an_unknown_key_and_changes_nothing(lib):
+    before = _state(lib)
+    ran = []
+    with pytest.raises(KeyError, match="conv_hallo"):
+        with tuned(lib, conv_small=0, conv_lean_geo=3, conv_hallo=0, conv_lean=0):
+            ran.append(1)
+    assert not ran and _state(lib) == before
+
+
+def test_conv_lean_geo_round_trips_through_minus_one(lib):
+    assert _state(lib)["conv_lean_geo"] == -1
+    with tuned(lib, conv_lean_geo=5):
+        assert _state(lib)["conv_lean_geo"] == 5
+        with tuned(lib, conv_lean_geo=-1):
+            assert _state(lib)["conv_lean_geo"] == -1
+        assert _state(lib)["conv_lean_geo"] == 5
+    assert _state(lib)["conv_lean_geo"] == -1
+
+
+def test_the_libraries_read_no_environment():
+    pkg = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mrfa_amd")
+    seen = 0
+    for sub in ("csrc", "csrc_data"):
+        for f in sorted(os.listdir(os.path.join(pkg, sub))):
+            seen += 1
+            assert "getenv" not in open(os.path.join(pkg, sub, f)).read(), f"{sub}/{f} reads the environment"
+    assert seen > 30

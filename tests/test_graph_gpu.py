@@ -459,8 +459,6 @@ def test_prologue_fusion_equals_the_bn_act_path(frames, monkeypatch):
     b, size = 1, 256                      # (the encoder's own maps: 64^2 x 32, 32^2 x 64, 16^2 x 128 -- the shapes conv_lean.hip / wgrad_lean.hip take)
     x = torch.cat([(det_uniform(f"pf/x{i}", (b, 3, size, size)) * (1.0 + 0.5 * i)).to(DEV) for i in range(frames)], 0)
     w = det_uniform("pf/w", (frames * b, 32, size // 4, size // 4)).to(DEV)
-    prev = hip.lib().mrfa_set_tuning(b"conv_lean_min_wgs", 1)           # (two frames do not make the workgroup count the bench batch does)
-    request_cleanup = lambda: hip.lib().mrfa_set_tuning(b"conv_lean_min_wgs", prev)
 
     def run(fused):
         monkeypatch.setattr(engine, "PROLOGUE_FUSION", fused)
@@ -475,12 +473,10 @@ def test_prologue_fusion_equals_the_bn_act_path(frames, monkeypatch):
         torch.cuda.synchronize()
         monkeypatch.setattr(engine.Ctx, "prebn", real)
         return y.detach(), {n: p.grad.double().clone() for n, p in m.named_parameters()}, {n: v.clone() for n, v in m.named_buffers()}, len(used)
-    try:
+    with hip.tuned(conv_lean_min_wgs=1):                                 # (two frames do not make the workgroup count the bench batch does)
         y0, g0, b0, n0 = run(False)
         y0b, g0b, _, _ = run(False)
         y1, g1, b1, n1 = run(True)
-    finally:
-        request_cleanup()
     assert n0 == 0 and n1 > 0, "the fused run must take the prologue path in its residual blocks"
     assert (y0 - y1).abs().max().item() <= 1e-5 * max(1.0, y0.abs().max().item())
     for n in b0:

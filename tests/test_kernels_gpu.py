@@ -378,15 +378,12 @@ def test_patch_tiled_kernel_is_run_to_run_identical(name):
     kw.pop("bn192", None)
     kw["stats"] = False
     assert L.mrfa_set_mfma_mode(1) == 0
-    prev = L.mrfa_set_tuning(b"conv_halo_min_tiles", 0)
-    L.mrfa_set_tuning(b"conv_small", 0); L.mrfa_set_tuning(b"conv_lean", 0)
     try:
-        outs = [conv_case(Side(True), tag=f"halo/{name}", wsplit=True, **kw)[0] for _ in range(8)]
-        assert L.mrfa_conv2d_last_config() & (1 << 28), "the patch-tiled kernel did not run"
+        with hip.tuned(conv_halo_min_tiles=0, conv_small=0, conv_lean=0):
+            outs = [conv_case(Side(True), tag=f"halo/{name}", wsplit=True, **kw)[0] for _ in range(8)]
+            assert L.mrfa_conv2d_last_config() & (1 << 28), "the patch-tiled kernel did not run"
     finally:
         L.mrfa_set_mfma_mode(0)
-        L.mrfa_set_tuning(b"conv_halo_min_tiles", prev)
-        L.mrfa_set_tuning(b"conv_small", 1); L.mrfa_set_tuning(b"conv_lean", 1)
     for o in outs[1:]:
         assert torch.equal(o, outs[0])
 
@@ -404,17 +401,13 @@ def test_conv2d_patch_tiled_kernel(name, mode):
     bn192 = kw.pop("bn192", 1)
     ref = conv_case(Side(False), tag=f"halo/{name}", **kw)
     assert L.mrfa_set_mfma_mode(mode) == 0
-    prev = L.mrfa_set_tuning(b"conv_halo_min_tiles", min_tiles)
-    L.mrfa_set_tuning(b"conv_small", 0); L.mrfa_set_tuning(b"conv_lean", 0)                     # (the small test shapes would otherwise go to conv_small.hip)
-    L.mrfa_set_tuning(b"conv_halo_bn192", bn192)
     try:
-        got = conv_case(Side(True), tag=f"halo/{name}", wsplit=("rne" if mode == 3 else True), **kw)
-        assert L.mrfa_conv2d_last_config() & (1 << 28), "the patch-tiled kernel did not run"
+        # (conv_small / conv_lean off: the small test shapes would otherwise go to conv_small.hip)
+        with hip.tuned(conv_halo_min_tiles=min_tiles, conv_small=0, conv_lean=0, conv_halo_bn192=bn192):
+            got = conv_case(Side(True), tag=f"halo/{name}", wsplit=("rne" if mode == 3 else True), **kw)
+            assert L.mrfa_conv2d_last_config() & (1 << 28), "the patch-tiled kernel did not run"
     finally:
         L.mrfa_set_mfma_mode(0)
-        L.mrfa_set_tuning(b"conv_halo_min_tiles", prev)
-        L.mrfa_set_tuning(b"conv_small", 1); L.mrfa_set_tuning(b"conv_lean", 1)
-        L.mrfa_set_tuning(b"conv_halo_bn192", 1)
     # mode 3: both operands rounded to 8 significand bits (2^-9 each), K = 288 .. 2304 products per output
     assert_close(ref, got, tol={1: 2e-4, 2: 2e-3, 3: 2e-2}[mode], what="halo " + name)
 
@@ -462,13 +455,12 @@ def _lean_run(name, mode, **over):
     kw.update(over)
     geo = kw.pop("geo")
     assert L.mrfa_set_mfma_mode(mode) == 0
-    L.mrfa_set_tuning(b"conv_lean_geo", geo)
     try:
-        got = conv_case(Side(True), tag=f"lean/{name}", wsplit=("rne" if mode == 3 else True), **kw)
-        assert L.mrfa_conv2d_last_config() & (1 << 27), "the lean patch kernel did not run"
+        with hip.tuned(conv_lean_geo=geo):
+            got = conv_case(Side(True), tag=f"lean/{name}", wsplit=("rne" if mode == 3 else True), **kw)
+            assert L.mrfa_conv2d_last_config() & (1 << 27), "the lean patch kernel did not run"
     finally:
         L.mrfa_set_mfma_mode(0)
-        L.mrfa_set_tuning(b"conv_lean_geo", -1)
     return got
 
 
@@ -505,12 +497,11 @@ def test_conv2d_gemm_lean_kernel(name, mode):
     kw = dict(GEMM_LEAN_CASES[name])
     ref = conv_case(Side(False), tag=f"glean/{name}", **kw)
     assert L.mrfa_set_mfma_mode(mode) == 0
-    prev = L.mrfa_set_tuning(b"gemm_lean", 2)          # 2: wherever it can run (1, the default, keeps it to the sizes it is faster at)
     try:
-        got = conv_case(Side(True), tag=f"glean/{name}", wsplit=("rne" if mode == 3 else True), **kw)
-        assert L.mrfa_conv2d_last_config() & (1 << 26), "the lean 1x1 kernel did not run"
+        with hip.tuned(gemm_lean=2):            # 2: wherever it can run (1, the default, keeps it to the sizes it is faster at)
+            got = conv_case(Side(True), tag=f"glean/{name}", wsplit=("rne" if mode == 3 else True), **kw)
+            assert L.mrfa_conv2d_last_config() & (1 << 26), "the lean 1x1 kernel did not run"
     finally:
-        L.mrfa_set_tuning(b"gemm_lean", prev)
         L.mrfa_set_mfma_mode(0)
     assert_close(ref, got, tol={1: 2e-4, 2: 2e-3, 3: 2e-2}[mode], what="gemm lean " + name)
 
@@ -528,14 +519,9 @@ def test_lean_kernel_is_run_to_run_identical_and_equals_the_one_wave_kernel():
         kw = dict(LEAN_CASES[name])
         kw.pop("geo")
         kw.update(stats=False, fin=False)
-        L.mrfa_set_tuning(b"conv_lean", 0)
-        L.mrfa_set_tuning(b"conv_halo", 0)
-        try:
+        with hip.tuned(conv_lean=0, conv_halo=0):
             small = conv_case(Side(True), tag=f"lean/{name}", **kw)[0]
             assert L.mrfa_conv2d_last_config() & 8, "not the one-wave-per-tile kernel"
-        finally:
-            L.mrfa_set_tuning(b"conv_lean", 1)
-            L.mrfa_set_tuning(b"conv_halo", 1)
         assert_close([small], [outs[0]], tol=2e-5, what="lean vs fp32 pipe " + name)
 
 
@@ -603,28 +589,23 @@ def test_patch_tiled_kernel_equals_the_row_tiled_kernel_and_fp64():
     side.call("mrfa_pack_conv_weights_multi", C.pointer(d), 1)
     errs = {}
     assert L.mrfa_set_mfma_mode(1) == 0
-    prev = L.mrfa_set_tuning(b"conv_halo_min_tiles", 0)
-    L.mrfa_set_tuning(b"conv_small", 0); L.mrfa_set_tuning(b"conv_lean", 0)
     try:
         for halo in (0, 1):
-            L.mrfa_set_tuning(b"conv_halo", halo)
-            y = side.garbage((N * H * W, Cout))
-            p = hip.ConvParams()
-            p.x, p.ldx, p.Hin, p.Win, p.ups, p.N, p.Cin = xd.data_ptr(), Cin, H, W, 0, N, Cin
-            p.w, p.w_ld, p.w_tap, p.kflat, p.w_rows = wp.data_ptr(), Cin, 128 * Cin, 0, 128
-            p.w_split, p.w_piece = wsb.data_ptr(), piece
-            p.y, p.ldy, p.Cout, p.Hout, p.Wout = y.data_ptr(), Cout, Cout, H, W
-            p.R, p.S, p.pad, p.alpha, p.nbatch, p.splitk = 3, 3, 1, 1.0, 1, 1
-            side.call("mrfa_conv2d_nhwc", C.byref(p))
-            assert bool(L.mrfa_conv2d_last_config() & (1 << 28)) == bool(halo)
-            torch.cuda.synchronize()
-            dlt = (y.double().cpu() - exact)
-            errs[halo] = (float(dlt.abs().max()), float(dlt.pow(2).mean().sqrt()))
+            with hip.tuned(conv_halo_min_tiles=0, conv_small=0, conv_lean=0, conv_halo=halo):
+                y = side.garbage((N * H * W, Cout))
+                p = hip.ConvParams()
+                p.x, p.ldx, p.Hin, p.Win, p.ups, p.N, p.Cin = xd.data_ptr(), Cin, H, W, 0, N, Cin
+                p.w, p.w_ld, p.w_tap, p.kflat, p.w_rows = wp.data_ptr(), Cin, 128 * Cin, 0, 128
+                p.w_split, p.w_piece = wsb.data_ptr(), piece
+                p.y, p.ldy, p.Cout, p.Hout, p.Wout = y.data_ptr(), Cout, Cout, H, W
+                p.R, p.S, p.pad, p.alpha, p.nbatch, p.splitk = 3, 3, 1, 1.0, 1, 1
+                side.call("mrfa_conv2d_nhwc", C.byref(p))
+                assert bool(L.mrfa_conv2d_last_config() & (1 << 28)) == bool(halo)
+                torch.cuda.synchronize()
+                dlt = (y.double().cpu() - exact)
+                errs[halo] = (float(dlt.abs().max()), float(dlt.pow(2).mean().sqrt()))
     finally:
         L.mrfa_set_mfma_mode(0)
-        L.mrfa_set_tuning(b"conv_halo", 1)
-        L.mrfa_set_tuning(b"conv_halo_min_tiles", prev)
-        L.mrfa_set_tuning(b"conv_small", 1); L.mrfa_set_tuning(b"conv_lean", 1)
     scale = float(exact.abs().max())
     assert errs[1][0] <= max(2.0 * errs[0][0], 1e-6 * scale) and errs[1][1] <= max(2.0 * errs[0][1], 1e-7 * scale), (errs, scale)
 
@@ -913,24 +894,18 @@ def test_wgrad_all_taps_kernel(cfg, mode):
     tag = "wgh/" + "_".join(f"{k}{v}" for k, v in cfg.items())
     ref = wgrad_case(Side(False), tag=tag, **cfg)
     assert L.mrfa_set_mfma_mode(mode) == 0
-    prev = L.mrfa_set_tuning(b"wgrad_halo_min_wgs", min_wgs)
-    L.mrfa_set_tuning(b"conv_small", 0); L.mrfa_set_tuning(b"conv_lean", 0)
     try:
-        got = wgrad_case(Side(True), tag=tag, **cfg)
-        plain = None
-        if cfg.get("ups"):           # the phase form of a fused-upsample layer against the nine-tap form of the same kernel
-            L.mrfa_set_tuning(b"wgrad_halo_phase", 0)
-            plain = wgrad_case(Side(True), tag=tag, **cfg)
-            L.mrfa_set_tuning(b"wgrad_halo_phase", 1)
-        # the same call with the kernel off must give the same answer from the per-tap kernels (and proves the switch works)
-        L.mrfa_set_tuning(b"wgrad_halo", 0)
-        other = wgrad_case(Side(True), tag=tag, **cfg)
+        with hip.tuned(wgrad_halo_min_wgs=min_wgs, conv_small=0, conv_lean=0):
+            got = wgrad_case(Side(True), tag=tag, **cfg)
+            plain = None
+            if cfg.get("ups"):           # the phase form of a fused-upsample layer against the nine-tap form of the same kernel
+                with hip.tuned(wgrad_halo_phase=0):
+                    plain = wgrad_case(Side(True), tag=tag, **cfg)
+            # the same call with the kernel off must give the same answer from the per-tap kernels (and proves the switch works)
+            with hip.tuned(wgrad_halo=0):
+                other = wgrad_case(Side(True), tag=tag, **cfg)
     finally:
         L.mrfa_set_mfma_mode(0)
-        L.mrfa_set_tuning(b"wgrad_halo", 1)
-        L.mrfa_set_tuning(b"wgrad_halo_phase", 1)
-        L.mrfa_set_tuning(b"wgrad_halo_min_wgs", prev)
-        L.mrfa_set_tuning(b"conv_small", 1); L.mrfa_set_tuning(b"conv_lean", 1)
     tol = {1: 5e-4, 2: 5e-3, 3: 3e-2}[mode]
     assert_close(ref, got, tol=tol, what=tag)
     assert_close(other, got, tol=tol, what=tag + " vs per-tap kernel")

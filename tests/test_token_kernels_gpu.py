@@ -60,6 +60,7 @@ MEASURED on an MI355X, largest err / bound per family (each test prints its own 
 The worst-case counts are loose where n or C is large (the attention ratios at n ~ 1000 are below 0.02); that the bounds still discriminate is shown by the
 mutants of tests/test_token_reference.py, not by these ratios.
 """
+import contextlib
 import functools
 import types
 
@@ -100,7 +101,7 @@ class Library:
         return hip.lib().mrfa_last_error().decode()
 
     def switch(self, value):
-        return hip.lib().mrfa_set_tuning(b"attention_mfma", int(value))
+        return hip.tuned(attention_mfma=value)
 
 
 class Spec:
@@ -118,7 +119,7 @@ class Spec:
         return self.emu.mrfa_last_error().decode()
 
     def switch(self, value):
-        return 1
+        return contextlib.nullcontext()
 
 
 def unwritten(shape):
@@ -238,18 +239,15 @@ def run_att(be, S, test, path="mfma", expect=None, keep=None):
         assert (fam_f, fam_b) == (expect or fams), (path, fam_f, fam_b, expect or fams)
         print(f"[{TAG}] attention d={d} n={n} B={B} heads={heads} {S.regime} [{path}]: forward {fam_f}<{d}>, backward {fam_b}<{d}>")
     bound = S.bounds["valu" if be.spec else fam_f]         # (the specification's forward is two-pass, as the VALU kernels')
-    prev = be.switch(sw[0])
-    try:
+    with be.switch(sw[0]):
         rc = be.call("mrfa_attention_fwd", bq.ptr, bq.ld, B, n, heads, d, S.scale, bo.ptr, bo.ld, bl.ptr)
         assert rc == 0, be.error()
         out, lse = bo.get(), bl.get()
         note(test, f"out[{fam_f}]", check(out, S.ref["out"], bound["out"], f"out [{fam_f}, {path}]"))
         note(test, f"lse[{fam_f}]", check(lse, S.ref["lse"], bound["lse"], f"lse [{fam_f}, {path}]"))
         out_bits, lse_bits = bo.bits(), bl.bits()
-        be.switch(sw[1])
-        rc = be.call("mrfa_attention_bwd", bq.ptr, bq.ld, bo.ptr, bo.ld, bdo.ptr, bdo.ld, bl.ptr, bdl.ptr, B, n, heads, d, S.scale, bdq.ptr, bdq.ld)
-    finally:
-        be.switch(prev)
+        with be.switch(sw[1]):
+            rc = be.call("mrfa_attention_bwd", bq.ptr, bq.ld, bo.ptr, bo.ld, bdo.ptr, bdo.ld, bl.ptr, bdl.ptr, B, n, heads, d, S.scale, bdq.ptr, bdq.ld)
     if fam_b == "refused" and not be.spec:
         msg = be.error()
         assert rc != 0 and "attention_bwd" in msg and "LDS" in msg, (rc, msg)

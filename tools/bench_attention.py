@@ -50,5 +50,5 @@ def graph_time(fn, reps=100):
 
 
 for mode in (0, 1, 0, 1):
-    L.mrfa_set_tuning(b"attention_mfma", mode)
-    print(f"attention_mfma={mode}: fwd {graph_time(fwd):6.1f} us   bwd (q + kv) {graph_time(bwd):6.1f} us", flush=True)
+    with hip.tuned(attention_mfma=mode):
+        print(f"attention_mfma={mode}: fwd {graph_time(fwd):6.1f} us   bwd (q + kv) {graph_time(bwd):6.1f} us", flush=True)

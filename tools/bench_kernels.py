@@ -131,22 +131,18 @@ def main():
             L = _hip.lib()
             res_ab = []
             for on in (0, 8, 9, 0, 8, 9):                      # off, 8-row patches with <= 128-wide tiles, 8-row patches with 256-wide tiles allowed
-                L.mrfa_set_tuning(b"conv_halo", int(on > 0))
-                L.mrfa_set_tuning(b"conv_halo_bn256", int(on == 9))
-                tf_ = time_it(lambda: e.conv(x, conv, out=out, relu=True, ups=bool(ups)), iters=a.iters)
-                used = bool(L.mrfa_conv2d_last_config() & (1 << 28))
-                td_ = time_it(lambda: e._conv_dgrad(x, cw, out, bool(ups), None), iters=a.iters)
-                used_d = bool(L.mrfa_conv2d_last_config() & (1 << 28))
+                with _hip.tuned(conv_halo=int(on > 0), conv_halo_bn256=int(on == 9)):
+                    tf_ = time_it(lambda: e.conv(x, conv, out=out, relu=True, ups=bool(ups)), iters=a.iters)
+                    used = bool(L.mrfa_conv2d_last_config() & (1 << 28))
+                    td_ = time_it(lambda: e._conv_dgrad(x, cw, out, bool(ups), None), iters=a.iters)
+                    used_d = bool(L.mrfa_conv2d_last_config() & (1 << 28))
                 res_ab.append((f"{on}{'*' if used else ' '}{'*' if used_d else ' '}", used, tf_, td_))
-            L.mrfa_set_tuning(b"conv_halo", 1)
-            L.mrfa_set_tuning(b"conv_halo_bn256", 1)
             wres = []
             for on in (0, 1, 0, 1):
-                L.mrfa_set_tuning(b"wgrad_halo", on)
-                tw_ = time_it(lambda: e._conv_wgrad(x, cw, out, bool(ups), None, True), iters=a.iters)
+                with _hip.tuned(wgrad_halo=on):
+                    tw_ = time_it(lambda: e._conv_wgrad(x, cw, out, bool(ups), None, True), iters=a.iters)
                 cw.dw_acc = None
                 wres.append(f"wg{on} {tf(tw_):5.1f}")
-            L.mrfa_set_tuning(b"wgrad_halo", 1)
             print(f"{name:42s} " + " ".join(f"h={on} f {tf(tf_):5.1f} d {tf(td_):5.1f} |"
                                              for on, used, tf_, td_ in res_ab) + "  " + " ".join(wres), flush=True)
             continue

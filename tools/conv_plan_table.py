@@ -16,7 +16,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from mrfa_amd.hip import ConvParams, WgradParams  # noqa: E402
+from mrfa_amd.hip import ConvParams, WgradParams, tuned  # noqa: E402
 
 # tuning switches of the table: (key, value) applied with mrfa_set_tuning on top of the defaults; None = defaults
 TUNINGS = [None, ("conv_small", 0), ("conv_halo", 0), ("conv_lean", 0), ("wgrad_halo", 0), ("wgrad_lean", 0), ("gemm_lean", 2)]
@@ -58,17 +58,13 @@ def open_lib(path):
 def answer(L, mode, tuning, struct, queries, ptr_names, ptrs, val_names, vals):
     """the answers of `queries` for every row, under matrix mode `mode` and the tuning switch `tuning`"""
     assert L.mrfa_set_mfma_mode(mode) == 0
-    prev = L.mrfa_set_tuning(tuning[0].encode(), tuning[1]) if tuning else None
-    try:
+    with tuned(L, **dict([tuning] if tuning else [])):
         out = np.zeros((len(vals), len(queries)), np.int16)
         for i in range(len(vals)):
             p = make_block(struct, ptr_names, ptrs[i], val_names, vals[i])
             for j, q in enumerate(queries):
                 out[i, j] = getattr(L, "mrfa_conv2d_" + q)(C.byref(p))
         return out
-    finally:
-        if tuning:
-            L.mrfa_set_tuning(tuning[0].encode(), prev)
 
 
 CH = [16, 32, 48, 64, 96, 128, 160, 192, 256, 320, 512, 576, 640, 1024]
