@@ -34,10 +34,14 @@ def graph_replay_safe(what: str = "hipGraph capture") -> None:
 __version__ = "0.2.0"
 
 _AUGMENT_EXPORTS = ("PairAugmenter", "PairParams", "PairDraw")      # mrfa_amd/augment.py, imported on first use (it imports torch)
+_RESIZE_EXPORTS = ("FrameResizer",)                                 # mrfa_amd/resize.py, likewise
 
 
 def __getattr__(name):
     if name in _AUGMENT_EXPORTS:
         from . import augment
         return getattr(augment, name)
+    if name in _RESIZE_EXPORTS:
+        from . import resize
+        return getattr(resize, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,5 +1,5 @@
 """Builds mrfa_amd/_lib/libmrfa_hip.so (all HIP kernels + the C ABI of include/mrfa_hip.h) and mrfa_amd/_lib/libmrfa_data_hip.so (the input pipeline's
-kernels, csrc_data/, + the C ABI of include/mrfa_data_hip.h) for gfx950 with hipcc.
+kernels, csrc_data/, + the C ABIs of include/mrfa_data_hip.h and include/mrfa_resize_hip.h) for gfx950 with hipcc.
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only build container; the resulting .so travels to the
 GPU box with the repo snapshot (it is git-ignored, not gpurun-ignored)."""
@@ -39,7 +39,8 @@ def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(LIBDIR, exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     headers = [os.path.join(ROOT, "include", "mrfa_hip.h")] + sorted(glob.glob(os.path.join(CSRC, "*.h")))
-    data_headers = headers + [os.path.join(ROOT, "include", "mrfa_data_hip.h")] + sorted(glob.glob(os.path.join(CSRC_DATA, "*.h")))
+    data_headers = headers + [os.path.join(ROOT, "include", h) for h in ("mrfa_data_hip.h", "mrfa_resize_hip.h")] \
+        + sorted(glob.glob(os.path.join(CSRC_DATA, "*.h")))
     units = [(CSRC, src, "", FLAGS, headers) for src in SOURCES] + [(CSRC_DATA, src, "data_", DATA_FLAGS, data_headers) for src in data_sources()]
     objs = {LIB: [], DATA_LIB: []}
     procs = []

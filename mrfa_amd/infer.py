@@ -77,12 +77,27 @@ def frames_to_uint8(frames: torch.Tensor, rounding: str = "nearest") -> torch.Te
     return _ctx(frames.device).frames_to_u8([FrameTile(frames.contiguous())], rounding=rounding)
 
 
-def _float_frames(frames: torch.Tensor, what: str) -> torch.Tensor:
-    """the frames of a public entry as fp32 (N,3,H,W): uint8 (N,H,W,C) frames are converted (one launch), fp32 frames pass through; told apart by dtype"""
+def _check_prepare(prepare, what: str):
+    """prepare=: None, or the mrfa_amd.resize.FrameResizer(output="float") that takes the place of frames_from_uint8 for byte frames of any size"""
+    if prepare is not None:
+        from .resize import FrameResizer
+        if not isinstance(prepare, FrameResizer) or prepare.output != "float":
+            raise ValueError(f"{what}: prepare is None or a FrameResizer(output=\"float\"), not {prepare!r}")
+    return prepare
+
+
+def _from_bytes(frames: torch.Tensor, prepare=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """byte frames (N,H,W,C) -> fp32 (N,3,.,.), one launch either way: frames_from_uint8, or `prepare` (crop and resize to its size)"""
+    return frames_from_uint8(frames, out=out) if prepare is None else prepare(frames, out=out)
+
+
+def _float_frames(frames: torch.Tensor, what: str, prepare=None) -> torch.Tensor:
+    """the frames of a public entry as fp32 (N,3,H,W): uint8 (N,H,W,C) frames are converted (one launch; `prepare`: cropped and resized in it), fp32 frames
+    pass through; told apart by dtype"""
     if torch.is_tensor(frames) and frames.dtype == torch.uint8:
         if frames.dim() != 4:
             raise ValueError(f"{what}: byte frames are uint8 (N,H,W,C), not {_describe(frames)}")
-        return frames_from_uint8(frames)
+        return _from_bytes(frames, prepare)
     return frames
 
 
@@ -155,7 +170,7 @@ class Visualizer:
 
 class Animator:
     def __init__(self, model: nn.Module, graph: bool = False, cache_dtype: torch.dtype = torch.float32, corr: str = "volume", relative: bool = False,
-                 adapt_movement_scale: bool = False, use_relative_jacobian: Optional[bool] = None, keep_warp: bool = False):
+                 adapt_movement_scale: bool = False, use_relative_jacobian: Optional[bool] = None, keep_warp: bool = False, prepare=None):
         """model: mrfa_amd.train.HotPath or mrfa_amd.modules.model.MRFA (attributes encoder / dense_motion / decoder / down).
         cache_dtype: storage of the cached source feature pyramid (RaftFlow.encode_source(feature_dtype=)); torch.bfloat16 halves what the cache holds
         and what the per-frame warps gather, at the cost of one rounding of the source features.
@@ -168,8 +183,12 @@ class Animator:
         one cached copy of every source (the frames of a clip, T at a time).  graph=True keeps one captured program per T it has seen.
         set_source, set_driving_initial and the call take fp32 (N,3,H,W) frames or uint8 (N,H,W,C) frames (frames_from_uint8), told apart by dtype; in
         graph mode byte frames are converted straight into the captured program's static driving buffer (one launch, no copy in between).
-        keep_warp: `warp` holds the decoder's warp_img (the source warped by the final flow) of the last call, beside the returned frames."""
+        keep_warp: `warp` holds the decoder's warp_img (the source warped by the final flow) of the last call, beside the returned frames.
+        prepare: a mrfa_amd.FrameResizer(size=(H, W)) that takes the place of frames_from_uint8 wherever byte frames come in: they may then have any size
+        (a decoded 1080p clip) and are cropped to its box and resized to the model's (H, W) in that one launch -- in graph mode straight into the captured
+        program's static driving buffer.  None: byte frames have the model's size already, exactly as before.  Float frames are never touched."""
         self.m = model.eval()
+        self.prepare = _check_prepare(prepare, "Animator")
         self.use_graph = graph
         self.cache_dtype = _check_cache_dtype(cache_dtype)
         self.corr = check_corr(corr)
@@ -197,7 +216,7 @@ class Animator:
         """driving_initial (relative mode): set_driving_initial(driving_initial) after the source.  A new source drops the captured programs AND an initial
         frame set earlier (the movement scale depends on both): pass it here or call set_driving_initial again."""
         m = self.m
-        source = _float_frames(source, "Animator.set_source")
+        source = _float_frames(source, "Animator.set_source", self.prepare)
         self.source = source
         self.kp_s = m.encoder(source)
         self.img_down = m.down(source)
@@ -214,7 +233,7 @@ class Animator:
         if not self.relative:
             raise ValueError("Animator.set_driving_initial: this Animator was built with relative=False and has no use for an initial driving frame")
         assert self.source is not None, "call set_source(source) first"
-        frame = _float_frames(frame, "Animator.set_driving_initial")
+        frame = _float_frames(frame, "Animator.set_driving_initial", self.prepare)
         if frame.shape[0] != self.source.shape[0]:
             raise ValueError(f"Animator.set_driving_initial: one initial driving frame per source ({frame.shape[0]} frames, {self.source.shape[0]} sources)")
         kp = {k: v for k, v in self.m.encoder(frame).items() if torch.is_tensor(v)}
@@ -259,11 +278,11 @@ class Animator:
             raise ValueError(f"Animator: byte frames are uint8 (N,H,W,C), not {_describe(driving)}")
         T = _frames_per_source(driving.shape[0], self.source.shape[0], "Animator")
         if not self.use_graph:
-            return self._run(frames_from_uint8(driving) if as_bytes else driving)
+            return self._run(_from_bytes(driving, self.prepare) if as_bytes else driving)
         if T not in self._graphs:                             # capture the program of T frames per source once per source and T
             from . import graph_replay_safe
             graph_replay_safe("Animator(graph=True)")
-            drv = frames_from_uint8(driving) if as_bytes else driving.clone()
+            drv = _from_bytes(driving, self.prepare) if as_bytes else driving.clone()
             eager = self._frame(drv).clone()                  # packs / tables outside the graph
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
@@ -283,7 +302,7 @@ class Animator:
             self._graphs[T] = (g, drv, out)
         g, drv, out = self._graphs[T]
         if as_bytes:
-            frames_from_uint8(driving, out=drv)               # straight into the program's static input: one launch
+            _from_bytes(driving, self.prepare, out=drv)       # straight into the program's static input: one launch
         else:
             drv.copy_(driving)
         g.replay()
@@ -375,9 +394,11 @@ class BestFrameSearch:
     until result().  graph=True keeps one captured program per group size T (the frame offset lives in the state, so one program serves every group); as
     with Animator(graph=True), do not run the model's modules eagerly between two replays of a capture."""
 
-    def __init__(self, model: nn.Module, graph: bool = False):
+    def __init__(self, model: nn.Module, graph: bool = False, prepare=None):
+        """prepare: as Animator's -- a FrameResizer for byte frames of any size, None for byte frames of the model's size"""
         self.m = model.eval()
         self.use_graph = graph
+        self.prepare = _check_prepare(prepare, "BestFrameSearch")
         self.kp_s: Optional[torch.Tensor] = None
         self.state: Optional[torch.Tensor] = None
         self._graphs: dict = {}                               # T -> (graph, static driving frames)
@@ -385,7 +406,7 @@ class BestFrameSearch:
     @torch.no_grad()
     def set_source(self, source: torch.Tensor):
         """the keypoints of the Bs sources and a fresh state; drops the captured programs (they hold the old tensors' addresses)"""
-        source = _float_frames(source, "BestFrameSearch.set_source")
+        source = _float_frames(source, "BestFrameSearch.set_source", self.prepare)
         self.kp_s = self.m.encoder(source)["kp"]
         self.state = pose_state(source.shape[0], source.device)
         self._graphs = {}
@@ -412,12 +433,12 @@ class BestFrameSearch:
             raise ValueError(f"BestFrameSearch: byte frames are uint8 (N,H,W,C), not {_describe(frames)}")
         T = _frames_per_source(frames.shape[0], self.kp_s.shape[0], "BestFrameSearch")
         if not self.use_graph:
-            self._group(frames_from_uint8(frames) if as_bytes else frames, self.state, False)
+            self._group(_from_bytes(frames, self.prepare) if as_bytes else frames, self.state, False)
             return
         if T not in self._graphs:                             # capture once per T, as Animator.__call__ does
             from . import graph_replay_safe
             graph_replay_safe("BestFrameSearch(graph=True)")
-            drv = frames_from_uint8(frames) if as_bytes else frames.clone()
+            drv = _from_bytes(frames, self.prepare) if as_bytes else frames.clone()
             eager = self._group(drv, pose_state(self.state.shape[0], self.state.device), True).clone()      # packs / tables outside the graph; a scratch state
             torch.cuda.synchronize()
             kept = self.state.clone()                         # the check replays below advance the state: put it back, whatever they find
@@ -436,7 +457,7 @@ class BestFrameSearch:
             self._graphs[T] = (g, drv)
         g, drv = self._graphs[T]
         if as_bytes:
-            frames_from_uint8(frames, out=drv)
+            _from_bytes(frames, self.prepare, out=drv)
         else:
             drv.copy_(frames)
         g.replay()
@@ -448,12 +469,13 @@ class BestFrameSearch:
 
 
 @torch.no_grad()
-def find_best_frame(model: nn.Module, source: torch.Tensor, driving_video: torch.Tensor, frames_per_call: int = 1, graph: bool = False) -> list:
+def find_best_frame(model: nn.Module, source: torch.Tensor, driving_video: torch.Tensor, frames_per_call: int = 1, graph: bool = False,
+                    prepare=None) -> list:
     """demo.py:75-98 on a driving clip (B,3,T,H,W): per source the index of the frame whose normalised keypoints are closest to the source's.  The keypoints
     are the model's K, not 68 face landmarks, so the index can differ from the reference's on the same clip.  frames_per_call frames per group (a shorter last
-    group at its own size); one host read, at the end."""
+    group at its own size); one host read, at the end.  prepare: BestFrameSearch's (byte sources and byte clips of any size)."""
     fpc = _check_frames_per_call(frames_per_call)
-    search = BestFrameSearch(model, graph=graph)
+    search = BestFrameSearch(model, graph=graph, prepare=prepare)
     search.set_source(source)
     n = _check_clip(driving_video, "find_best_frame")         # (a byte clip (B,T,H,W,C) and byte sources go in as they are)
     for t0 in range(0, n, fpc):
@@ -548,7 +570,7 @@ def _clip_group(video: torch.Tensor, t0: int, T: int) -> torch.Tensor:
 
 @torch.no_grad()
 def reconstruction(model: nn.Module, video: torch.Tensor, graph: bool = False, cache_dtype: torch.dtype = torch.float32, corr: str = "volume",
-                   frames_per_call: int = 1, metrics: str = "host", output: str = "float", visualize: bool = False):
+                   frames_per_call: int = 1, metrics: str = "host", output: str = "float", visualize: bool = False, prepare=None):
     """The reference's reconstruction loop (reconstruction.py:52-70) on one clip: source = frame 0, driving = every frame t,
     metrics mean|out - driving| and PSNR per frame.  video: (B,3,T,H,W) in [0,1].  The source is fixed for the whole clip, so
     the source half of the path is computed once (Animator).  frames_per_call: that many frames of the clip run as one batch against the one cached
@@ -563,13 +585,16 @@ def reconstruction(model: nn.Module, video: torch.Tensor, graph: bool = False, c
     computed on the fp32 frames, as before.
     visualize=True adds 'visualization': uint8 (T, B H, 4 W, 3), per frame one Visualizer().visualize(source, driving, cat([warp_img, out], 3)) as
     reconstruction.py:65-67 builds it -- source | driving | warped source | prediction, the B sources stacked downwards.  warp_img is the decoder's; if
-    its size differs from the frame's it is resized with the engine's bilinear resize before composing."""
+    its size differs from the frame's it is resized with the engine's bilinear resize before composing.
+    prepare: a FrameResizer for a byte clip of any size (Animator's `prepare`): every group of frames is cropped and resized on the device, and the metrics
+    and the visualisation are taken on those resized floats."""
     fpc = _check_frames_per_call(frames_per_call)
+    _check_prepare(prepare, "reconstruction")
     if metrics not in ("host", "device"):
         raise ValueError(f"reconstruction: metrics must be \"host\" or \"device\", not {metrics!r}")
     _check_output(output, "reconstruction")
     n = _check_clip(video, "reconstruction")
-    anim = Animator(model, graph=graph, cache_dtype=cache_dtype, corr=corr, keep_warp=bool(visualize))
+    anim = Animator(model, graph=graph, cache_dtype=cache_dtype, corr=corr, keep_warp=bool(visualize), prepare=prepare)
     anim.set_source(_clip_frame(video, 0))
     bs = video.shape[0]
     vis = _ClipVisualization(anim) if visualize else None
@@ -578,7 +603,7 @@ def reconstruction(model: nn.Module, video: torch.Tensor, graph: bool = False, c
     preds, l1, ps = [], [], []
     for t0 in range(0, n, fpc):
         T = min(fpc, n - t0)
-        group = _float_frames(_clip_group(video, t0, T), "reconstruction")
+        group = _float_frames(_clip_group(video, t0, T), "reconstruction", prepare)
         outs = anim(group)
         if vis is not None:
             vis.add(group, outs, T)
@@ -632,7 +657,7 @@ def _reconstruction_device_metrics(anim: Animator, video: torch.Tensor, fpc: int
     cm, preds, sizes = ClipMetrics(ssim=True), [], []
     for t0 in range(0, n, fpc):
         T = min(fpc, n - t0)
-        driving = _float_frames(_clip_group(video, t0, T), "reconstruction")
+        driving = _float_frames(_clip_group(video, t0, T), "reconstruction", anim.prepare)
         outs = anim(driving).contiguous()
         cm.add(outs, driving)
         if vis is not None:
@@ -652,7 +677,7 @@ def _reconstruction_device_metrics(anim: Animator, video: torch.Tensor, fpc: int
 @torch.no_grad()
 def make_animation(model: nn.Module, source: torch.Tensor, driving_video: torch.Tensor, relative: bool = True,
                    adapt_movement_scale: bool = False, graph: bool = False, cache_dtype: torch.dtype = torch.float32, corr: str = "volume",
-                   frames_per_call: int = 1, initial_frame=0, output: str = "float"):
+                   frames_per_call: int = 1, initial_frame=0, output: str = "float", prepare=None):
     """demo.py:47-73 / animate_ddp.py:88-105: animate ONE source by the motion of a driving clip (B,3,T,H,W); with
     relative=True the driving keypoints go through normalize_kp against driving frame `initial_frame` (0: the first, as the reference's loop; the index of
     demo.py:150-157's best frame gives that branch's clip in one pass, since every frame depends on the initial one alone).  initial_frame: an index for
@@ -661,18 +686,21 @@ def make_animation(model: nn.Module, source: torch.Tensor, driving_video: torch.
     frames of the clip run as one batch against the one cached source (a shorter last group at its own size).  graph=True replays one captured program per
     group size.  One loop over an Animator(relative=relative, ...) in every mode.  Returns (B,3,T,H,W).
     The source may be uint8 (B,H,W,C) and the clip uint8 (B,T,H,W,C), C in {1,3,4}, as an image reader returns them (frames_from_uint8 on the device).
-    output="uint8" returns uint8 (B,T,H,W,3), each group of frames rounded to nearest on the device (img_as_ubyte, demo.py:160)."""
+    output="uint8" returns uint8 (B,T,H,W,3), each group of frames rounded to nearest on the device (img_as_ubyte, demo.py:160).
+    prepare: a FrameResizer for a byte source and a byte clip of any size (Animator's `prepare`; the best-frame search uses it too)."""
     fpc = _check_frames_per_call(frames_per_call)
+    _check_prepare(prepare, "make_animation")
     _check_output(output, "make_animation")
     bs, n = source.shape[0], _check_clip(driving_video, "make_animation")
     if isinstance(initial_frame, str) and initial_frame == "best":
-        initial_frame = find_best_frame(model, source, driving_video, frames_per_call=fpc, graph=graph) if relative else 0
+        initial_frame = find_best_frame(model, source, driving_video, frames_per_call=fpc, graph=graph, prepare=prepare) if relative else 0
     per_source = isinstance(initial_frame, (list, tuple))
     indices = list(initial_frame) if per_source else [initial_frame]
     if (per_source and len(indices) != bs) or not all(isinstance(i, int) and 0 <= i < n for i in indices):
         raise ValueError(f"initial_frame must be the index of one of the clip's {n} frames, a sequence of {bs} such indices (one per source) or \"best\", "
                          f"not {initial_frame!r}")
-    anim = Animator(model, graph=graph, cache_dtype=cache_dtype, corr=corr, relative=relative, adapt_movement_scale=adapt_movement_scale)
+    anim = Animator(model, graph=graph, cache_dtype=cache_dtype, corr=corr, relative=relative, adapt_movement_scale=adapt_movement_scale,
+                    prepare=prepare)
     if per_source:                                            # Animator.set_driving_initial takes one frame per source: frame indices[s] of source s
         initial = torch.stack([_clip_frame(driving_video[s:s + 1], i)[0] for s, i in enumerate(indices)], dim=0)
     else:
