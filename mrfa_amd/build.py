@@ -1,4 +1,4 @@
-"""Builds mrfa_amd/_lib/libmrfa_hip.so (all HIP kernels + the C ABI of include/mrfa_hip.h) and mrfa_amd/_lib/libmrfa_data_hip.so (the input pipeline's
+"""Builds mrfa_amd/_lib/libmrfa_hip.so (all HIP kernels + the C ABIs of include/mrfa_hip.h and include/mrfa_equiv_hip.h) and mrfa_amd/_lib/libmrfa_data_hip.so (the input pipeline's
 kernels, csrc_data/, + the C ABIs of include/mrfa_data_hip.h and include/mrfa_resize_hip.h) for gfx950 with hipcc.
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only build container; the resulting .so travels to the
@@ -13,7 +13,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "_lib")
 LIB = os.path.join(LIBDIR, "libmrfa_hip.so")
-SOURCES = ["error.cpp", "conv_plan.hip", "conv_mfma.hip", "conv_split.hip", "conv_halo.hip", "conv_small.hip", "conv_lean.hip", "wgrad_mfma.hip", "wgrad_split.hip", "wgrad_halo.hip", "wgrad_small.hip", "wgrad_lean.hip", "conv_fewout.hip", "conv_fewout3.hip", "layout.hip", "pack_multi.hip", "norm.hip", "sample.hip", "elementwise.hip", "optim.hip", "tokenpose.hip", "attention_mfma.hip", "losses.hip", "prior.hip", "pose.hip", "metrics.hip", "frames.hip"]
+SOURCES = ["error.cpp", "conv_plan.hip", "conv_mfma.hip", "conv_split.hip", "conv_halo.hip", "conv_small.hip", "conv_lean.hip", "wgrad_mfma.hip", "wgrad_split.hip", "wgrad_halo.hip", "wgrad_small.hip", "wgrad_lean.hip", "conv_fewout.hip", "conv_fewout3.hip", "layout.hip", "pack_multi.hip", "norm.hip", "sample.hip", "elementwise.hip", "optim.hip", "tokenpose.hip", "attention_mfma.hip", "losses.hip", "prior.hip", "pose.hip", "metrics.hip", "frames.hip", "equivariance.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
          "-Wno-unused-result"]
 # the data library: every kernel of csrc_data/ plus its own error / version file.  Its arithmetic is specified operation by operation (augment_math.h), so no
@@ -38,7 +38,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     """builds both libraries; returns the model library's path (the data library is DATA_LIB)"""
     os.makedirs(LIBDIR, exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    headers = [os.path.join(ROOT, "include", "mrfa_hip.h")] + sorted(glob.glob(os.path.join(CSRC, "*.h")))
+    headers = [os.path.join(ROOT, "include", h) for h in ("mrfa_hip.h", "mrfa_equiv_hip.h")] + sorted(glob.glob(os.path.join(CSRC, "*.h")))
     data_headers = headers + [os.path.join(ROOT, "include", h) for h in ("mrfa_data_hip.h", "mrfa_resize_hip.h")] \
         + sorted(glob.glob(os.path.join(CSRC_DATA, "*.h")))
     units = [(CSRC, src, "", FLAGS, headers) for src in SOURCES] + [(CSRC_DATA, src, "data_", DATA_FLAGS, data_headers) for src in data_sources()]

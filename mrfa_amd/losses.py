@@ -10,7 +10,8 @@ slice reduced by one kernel each (K22).  The real image's branch runs without a 
 backward is the data-gradient chain only.  Pretrained VGG19 weights (torchvision, downloaded by the reference) do not exist
 offline: `Vgg19(state_dict=...)` takes the `state_dict()` of the reference's Vgg19 module (same parameter names); without it
 the weights are a deterministic random initialisation and only the ARITHMETIC of the loss is comparable (tests use the same
-weights on both sides).  Transform and the equivariance terms act on (B,10,2) tensors and one image warp: torch device ops.
+weights on both sides).  Transform and the equivariance terms act on (B,10,2) tensors and one image warp: torch device ops by
+default; GeneratorFullLoss(equivariance="library") runs them as the three launches of mrfa_amd.equivariance instead.
 The background term (model.py:248-253) uses mrfa_amd.modules.BGMotionPredictor (resnet18 on the engine).
 """
 from __future__ import annotations
@@ -211,14 +212,26 @@ def _inv2x2(m):
 
 class GeneratorFullLoss(nn.Module):
     """loss_values of MRFA.forward(is_train=True), model.py:219-246 (without the background term): 'perceptual', 'equivariance',
-    'equivariance_jacobian'.  `encoder` is the model's keypoint encoder (third pass on the warped driving frame, model.py:234)."""
+    'equivariance_jacobian'.  `encoder` is the model's keypoint encoder (third pass on the warped driving frame, model.py:234).
+    equivariance: "torch" computes the frame warp's grid and the two equivariance terms with torch ops (the Jacobian through a double backward),
+    "library" with the closed-form kernels of mrfa_amd.equivariance (include/mrfa_equiv_hip.h); the same Transform draw feeds either."""
 
-    def __init__(self, train_params: dict, vgg: Optional[Vgg19] = None):
+    def __init__(self, train_params: dict, vgg: Optional[Vgg19] = None, equivariance: str = "torch"):
         super().__init__()
+        if equivariance not in ("torch", "library"):
+            raise ValueError(f"GeneratorFullLoss: equivariance must be \"torch\" or \"library\", not {equivariance!r}")
+        self.equivariance = equivariance
         self.train_params = train_params
         self.scales = train_params['scales']
         self.loss_weights = train_params['loss_weights']
         self.perceptual = PerceptualLoss(self.scales, self.loss_weights['perceptual'], vgg) if sum(self.loss_weights['perceptual']) != 0 else None
+
+    def transform_frame(self, transform: Transform, frame: torch.Tensor) -> torch.Tensor:
+        """the frame warped by `transform`, on the path this loss was built with"""
+        if self.equivariance == "library":
+            from .equivariance import transform_frame
+            return transform_frame(transform, frame)
+        return transform.transform_frame(frame)
 
     def forward(self, encoder: nn.Module, driving: torch.Tensor, generated: torch.Tensor, kp_driving: Dict[str, torch.Tensor],
                 transform: Optional[Transform] = None, bg_param: Optional[torch.Tensor] = None,
@@ -232,15 +245,19 @@ class GeneratorFullLoss(nn.Module):
             if transform is None:
                 transform = Transform(driving.shape[0], device=driving.device, **self.train_params['transform_params'])
             if transformed_kp is None:
-                transformed_kp = encoder(transform.transform_frame(driving))
-            value = torch.abs(kp_driving['kp'] - transform.warp_coordinates(transformed_kp['kp'])).mean()
-            out['equivariance'] = w['equivariance'] * value
-            if w['equivariance_jacobian'] != 0:
-                jt = torch.matmul(transform.jacobian(transformed_kp['kp']), transformed_kp['jacobian'])
-                value = torch.matmul(_inv2x2(kp_driving['jacobian']), jt)
-                eye = torch.eye(2, device=value.device, dtype=value.dtype).view(1, 1, 2, 2)
-                # model.py:245 keeps the un-reduced |I - J| tensor; train.py:62 then takes .mean() of every loss value
-                out['equivariance_jacobian'] = w['equivariance_jacobian'] * torch.abs(eye - value)
+                transformed_kp = encoder(self.transform_frame(transform, driving))
+            if self.equivariance == "library":
+                from .equivariance import equivariance_terms
+                out.update(equivariance_terms(transform, kp_driving, transformed_kp, w['equivariance'], w['equivariance_jacobian']))
+            else:
+                value = torch.abs(kp_driving['kp'] - transform.warp_coordinates(transformed_kp['kp'])).mean()
+                out['equivariance'] = w['equivariance'] * value
+                if w['equivariance_jacobian'] != 0:
+                    jt = torch.matmul(transform.jacobian(transformed_kp['kp']), transformed_kp['jacobian'])
+                    value = torch.matmul(_inv2x2(kp_driving['jacobian']), jt)
+                    eye = torch.eye(2, device=value.device, dtype=value.dtype).view(1, 1, 2, 2)
+                    # model.py:245 keeps the un-reduced |I - J| tensor; train.py:62 then takes .mean() of every loss value
+                    out['equivariance_jacobian'] = w['equivariance_jacobian'] * torch.abs(eye - value)
         if bg_param is not None:                                           # model.py:248-253: forward o reverse background motion = identity
             value = torch.matmul(bg_param, bg_param_reverse)
             eye = torch.eye(3, device=value.device, dtype=value.dtype).view(1, 3, 3)

@@ -22,7 +22,8 @@ def _get(cfg, key):
 class MRFA(nn.Module):
     """attributes used by the reference's callers: .encoder .dense_motion .decoder .down (train.py:21-24, demo.py:40-42)"""
 
-    def __init__(self, cfg, **kwargs):
+    def __init__(self, cfg, equivariance: str = "torch", **kwargs):
+        """equivariance: "torch" or "library", the path of the equivariance terms (mrfa_amd.losses.GeneratorFullLoss)"""
         super().__init__()
         self.cfg = cfg
         train_params = _get(cfg, 'train_params')
@@ -34,7 +35,7 @@ class MRFA(nn.Module):
         object.__setattr__(self, 'losses', None)
         if 'loss_weights' in train_params and 'scales' in train_params:
             from ..losses import GeneratorFullLoss, ImagePyramide
-            full = GeneratorFullLoss(train_params)
+            full = GeneratorFullLoss(train_params, equivariance=equivariance)
             self.scales = train_params['scales']
             self.loss_weights = train_params['loss_weights']
             if full.perceptual is not None:

@@ -212,7 +212,7 @@ def reference_loss(model: HotPath, full_loss, source, driving) -> torch.Tensor:
         # the third encoder pass (model.py:232-234) depends on the driving frame only: issued together with the first two
         from .losses import Transform
         transform = Transform(driving.shape[0], device=driving.device, **full_loss.train_params['transform_params'])
-        kp_s, kp_d, transformed_kp = model.encode_many([source, driving, transform.transform_frame(driving)])
+        kp_s, kp_d, transformed_kp = model.encode_many([source, driving, full_loss.transform_frame(transform, driving)])
     else:
         kp_s, kp_d = model.encode_pair(source, driving)
     model.await_packs()
