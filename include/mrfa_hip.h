@@ -523,7 +523,8 @@ int mrfa_antialias_down_bwd(void* stream, const float* dy, int lddy, int N, int 
  *
  * K15  kp2gaussian (reference modules/util.py:59-87) on the [-1,1]^2 grid of make_coordinate_grid (util.py:90-108), written into
  *      an NHWC view (channel k of out row (b,y,x)):  out = exp(-0.5 |g(y,x) - kp[b,k]|^2 / variance) [+ pos[k,y,x]]
- *      (pos = RaftFlow.pos_embedding (1,K,H,W), raft.py:177-178; may be null).  Backward: dkp (B,K,2) += , dpos (K,H,W) += .   */
+ *      (pos = RaftFlow.pos_embedding (1,K,H,W), raft.py:177-178; may be null).  Backward: dkp (B,K,2) += , dpos (K,H,W) += .
+ *      Refused with a message (outputs untouched): a null kp / out / dout; B or K < 1; H or W < 2; variance <= 0; ldo or lddo < K.   */
 int mrfa_kp_gaussian_fwd(void* stream, const float* kp, const float* pos, int B, int K, int H, int W, float variance, float* out, int ldo);
 int mrfa_kp_gaussian_bwd(void* stream, const float* kp, int B, int K, int H, int W, float variance, const float* dout, int lddo,
                          float* dkp /*+=, may be null*/, float* dpos /*+=, may be null*/);
@@ -539,7 +540,9 @@ int mrfa_kp_gaussian_bwd(void* stream, const float* kp, int B, int K, int H, int
  * sparse (B, K+1, C, H, W) dense = the returned `sparse_deformed` (may be null).
  * Backward reads dinp (same geometry as inp, lddi), dmotions (gradient of `motions` from K17, same ldm; may be null), dsparse
  * (may be null) and adds into dkd, dks (B,K,2), djd, djs (B,K,4), dbg (B,9) (each may be null); the source image gets no
- * gradient (it is the network input).                                                                            */
+ * gradient (it is the network input).
+ * Refused with a message (outputs untouched): a null kd / ks / src / motions / inp (forward) / dinp (backward); B, K or C < 1; C > 8; H or W < 2;
+ * jd without js or js without jd; ldm < 2; lds < C; ldi or lddi < (K+1)(C+1); in the backward djd or djs given without jd / js, and dbg without bg.  */
 typedef struct mrfa_prior_params {
     const float *kd, *ks, *jd, *js, *bg;
     const float* src; int lds;
@@ -572,7 +575,9 @@ int mrfa_kp_relative_fwd(void* stream, const float* kp_d, const float* jac_d, co
 /* K14+K17: mask = softmax over the K1 = K+1 motions of logit (B,H,W,K1 NHWC, ldl); deformation (B,H,W,2) = sum_k mask_k motion_k
  * (reference modules/dense_motion.py:129-136); also exports mask and the logits as NCHW (B,K1,H,W) (the returned `mask`,
  * `logit_mask`).  Backward: dlogit (NHWC view, lddl) += softmax backward of (ddeformation . motion_k + dmask_k) + dlogit_nchw,
- * dmotions (same geometry as motions) += mask_k ddeformation.  ddeformation / dmask / dlogit_nchw / dmotions may be null.   */
+ * dmotions (same geometry as motions) += mask_k ddeformation.  ddeformation / dmask / dlogit_nchw / dmotions may be null.
+ * Refused with a message (outputs untouched): a null logit / motions / deformation / mask_nchw / logit_nchw (forward), motions / mask_nchw / dlogit
+ * (backward); K1 < 1 or K1 > 32; B, H or W < 1; ldl or lddl < K1; ldm < 2.                                                    */
 int mrfa_softmax_combine_fwd(void* stream, const float* logit, int ldl, const float* motions, int ldm, int B, int H, int W, int K1,
                              float* deformation, float* mask_nchw, float* logit_nchw);
 int mrfa_softmax_combine_bwd(void* stream, const float* motions, int ldm, int B, int H, int W, int K1, const float* mask_nchw,
@@ -581,7 +586,10 @@ int mrfa_softmax_combine_bwd(void* stream, const float* motions, int ldm, int B,
 
 /* K14: KPDetector head (reference modules/kp_detector.py:90-120): heat = softmax over the H*W positions of logits[b,:,:,k] / T,
  * kp[b,k] = sum heat * grid, jac[b,k,:] = sum heat * jm[b,:,:,0..3] (jm: the 4 Jacobian maps, NHWC, may be null).  stat (B,K,2)
- * receives (max, 1/sum) for the backward, which recomputes heat:  dlogits (NHWC view, lddl) +=, djm (lddj) += .           */
+ * receives (max, 1/sum) for the backward, which recomputes heat:  dlogits (NHWC view, lddl) +=, djm (lddj) += .
+ * In the backward dkp or djac may be null (a null gradient is zero), and djm may be null when djac is given (dlogits alone is written).
+ * Refused with a message (outputs untouched): a null logits / kp / stat (/ dlogits); B or K < 1; H or W < 2; temperature <= 0; ldl or lddl < K;
+ * jm without jac in the forward, jm and djac without jac in the backward; ldj < 4 when jm is given; lddj < 4 when jm, djac and djm are given.  */
 int mrfa_kp_head_fwd(void* stream, const float* logits, int ldl, const float* jm, int ldj, int B, int H, int W, int K, float temperature,
                      float* kp, float* jac, float* stat);
 int mrfa_kp_head_bwd(void* stream, const float* logits, int ldl, const float* jm, int ldj, int B, int H, int W, int K, float temperature,

@@ -414,6 +414,7 @@ __global__ __launch_bounds__(NT) void kp_head_bwd_kernel(const float* __restrict
 extern "C" int mrfa_kp_gaussian_fwd(void* stream, const float* kp, const float* pos, int B, int K, int H, int W, float variance, float* out,
                                     int ldo) {
     MRFA_CHECK_ARG(kp && out && B > 0 && K > 0 && H > 1 && W > 1 && variance > 0.f, "kp_gaussian_fwd: bad arguments");
+    MRFA_CHECK_ARG(ldo >= K, "kp_gaussian_fwd: ldo %d is less than K %d", ldo, K);
     const long long total = (long long)B * H * W * K;
     hipLaunchKernelGGL(kp_gaussian_fwd_kernel, dim3(stream_grid(total, NT)), dim3(NT), 0, (hipStream_t)stream, kp, pos, B, K, H, W,
                        1.f / variance, out, ldo);
@@ -424,6 +425,7 @@ extern "C" int mrfa_kp_gaussian_fwd(void* stream, const float* kp, const float* 
 extern "C" int mrfa_kp_gaussian_bwd(void* stream, const float* kp, int B, int K, int H, int W, float variance, const float* dout, int lddo,
                                     float* dkp, float* dpos) {
     MRFA_CHECK_ARG(kp && dout && B > 0 && K > 0 && H > 1 && W > 1 && variance > 0.f, "kp_gaussian_bwd: bad arguments");
+    MRFA_CHECK_ARG(lddo >= K, "kp_gaussian_bwd: lddo %d is less than K %d", lddo, K);
     hipLaunchKernelGGL(kp_gaussian_bwd_kernel, dim3(B * K), dim3(NT), 0, (hipStream_t)stream, kp, B, K, H, W, 1.f / variance, dout, lddo, dkp,
                        dpos);
     MRFA_CHECK_LAUNCH("mrfa_kp_gaussian_bwd");
@@ -452,6 +454,8 @@ extern "C" int mrfa_prior_motion_bwd(void* stream, const mrfa_prior_params* pp) 
     const mrfa_prior_params& p = *pp;
     if (int rc = check_prior(p, "prior_motion_bwd")) return rc;
     MRFA_CHECK_ARG(p.dinp && p.lddi >= (p.K + 1) * (p.C + 1), "prior_motion_bwd: gradient of the hourglass input buffer");
+    MRFA_CHECK_ARG(p.jd || (!p.djd && !p.djs), "prior_motion_bwd: djd / djs given without jd / js");
+    MRFA_CHECK_ARG(p.bg || !p.dbg, "prior_motion_bwd: dbg given without bg");
     hipLaunchKernelGGL(prior_motion_bwd_kernel, dim3(p.B * (p.K + 1)), dim3(NT), 0, (hipStream_t)stream, p);
     MRFA_CHECK_LAUNCH("mrfa_prior_motion_bwd");
     return 0;
@@ -480,6 +484,8 @@ extern "C" int mrfa_softmax_combine_fwd(void* stream, const float* logit, int ld
                                         float* deformation, float* mask, float* logit_nchw) {
     MRFA_CHECK_ARG(logit && motions && deformation && mask && logit_nchw && K1 > 0 && K1 <= MAXK1, "softmax_combine_fwd: bad arguments (K1 <= %d)",
                    MAXK1);
+    MRFA_CHECK_ARG(B > 0 && H > 0 && W > 0, "softmax_combine_fwd: B, H and W must be > 0 (B %d, H %d, W %d)", B, H, W);
+    MRFA_CHECK_ARG(ldl >= K1 && ldm >= 2, "softmax_combine_fwd: bad leading dimensions (ldl %d < K1 %d or ldm %d < 2)", ldl, K1, ldm);
     const long long total = (long long)B * H * W;
     hipLaunchKernelGGL(softmax_combine_fwd_kernel, dim3(stream_grid(total, NT)), dim3(NT), 0, (hipStream_t)stream, logit, ldl, motions, ldm, B,
                        H * W, K1, deformation, mask, logit_nchw);
@@ -490,7 +496,9 @@ extern "C" int mrfa_softmax_combine_fwd(void* stream, const float* logit, int ld
 extern "C" int mrfa_softmax_combine_bwd(void* stream, const float* motions, int ldm, int B, int H, int W, int K1, const float* mask,
                                         const float* ddeformation, const float* dmask, const float* dlogit_nchw, float* dlogit, int lddl,
                                         float* dmotions) {
-    MRFA_CHECK_ARG(motions && mask && dlogit && K1 > 0 && K1 <= MAXK1, "softmax_combine_bwd: bad arguments");
+    MRFA_CHECK_ARG(motions && mask && dlogit && K1 > 0 && K1 <= MAXK1, "softmax_combine_bwd: bad arguments (K1 <= %d)", MAXK1);
+    MRFA_CHECK_ARG(B > 0 && H > 0 && W > 0, "softmax_combine_bwd: B, H and W must be > 0 (B %d, H %d, W %d)", B, H, W);
+    MRFA_CHECK_ARG(lddl >= K1 && ldm >= 2, "softmax_combine_bwd: bad leading dimensions (lddl %d < K1 %d or ldm %d < 2)", lddl, K1, ldm);
     const long long total = (long long)B * H * W;
     hipLaunchKernelGGL(softmax_combine_bwd_kernel, dim3(stream_grid(total, NT)), dim3(NT), 0, (hipStream_t)stream, motions, ldm, B, H * W, K1,
                        mask, ddeformation, dmask, dlogit_nchw, dlogit, lddl, dmotions);
@@ -502,6 +510,7 @@ extern "C" int mrfa_kp_head_fwd(void* stream, const float* logits, int ldl, cons
                                 float temperature, float* kp, float* jac, float* stat) {
     MRFA_CHECK_ARG(logits && kp && stat && B > 0 && K > 0 && H > 1 && W > 1 && temperature > 0.f, "kp_head_fwd: bad arguments");
     MRFA_CHECK_ARG(jm == nullptr || jac != nullptr, "kp_head_fwd: jacobian maps without an output");
+    MRFA_CHECK_ARG(ldl >= K && (jm == nullptr || ldj >= 4), "kp_head_fwd: bad leading dimensions (ldl %d < K %d, or ldj %d < 4 with maps)", ldl, K, ldj);
     hipLaunchKernelGGL(kp_head_fwd_kernel, dim3(B * K), dim3(NT), 0, (hipStream_t)stream, logits, ldl, jm, ldj, B, H, W, K, 1.f / temperature, kp,
                        jac, stat);
     MRFA_CHECK_LAUNCH("mrfa_kp_head_fwd");
@@ -511,7 +520,10 @@ extern "C" int mrfa_kp_head_fwd(void* stream, const float* logits, int ldl, cons
 extern "C" int mrfa_kp_head_bwd(void* stream, const float* logits, int ldl, const float* jm, int ldj, int B, int H, int W, int K,
                                 float temperature, const float* kp, const float* jac, const float* stat, const float* dkp, const float* djac,
                                 float* dlogits, int lddl, float* djm, int lddj) {
-    MRFA_CHECK_ARG(logits && kp && stat && dlogits && B > 0 && K > 0 && temperature > 0.f, "kp_head_bwd: bad arguments");
+    MRFA_CHECK_ARG(logits && kp && stat && dlogits && B > 0 && K > 0 && H > 1 && W > 1 && temperature > 0.f, "kp_head_bwd: bad arguments");
+    MRFA_CHECK_ARG(!(jm && djac) || jac != nullptr, "kp_head_bwd: jacobian maps and djac without the forward's jac");
+    MRFA_CHECK_ARG(ldl >= K && lddl >= K && (jm == nullptr || ldj >= 4) && (!(jm && djac && djm) || lddj >= 4),
+                   "kp_head_bwd: bad leading dimensions (ldl %d or lddl %d < K %d, or ldj %d / lddj %d < 4 with maps)", ldl, lddl, K, ldj, lddj);
     const long long total = (long long)B * H * W;
     hipLaunchKernelGGL(kp_head_bwd_kernel, dim3(stream_grid(total, NT)), dim3(NT), 0, (hipStream_t)stream, logits, ldl, jm, ldj, B, H, W, K,
                        1.f / temperature, kp, jac, stat, dkp, djac, dlogits, lddl, djm, lddj);

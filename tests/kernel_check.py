@@ -1,4 +1,5 @@
-"""What the per-element kernel tests share (tests/test_sample_kernels_gpu.py, tests/test_token_kernels_gpu.py, tests/test_norm_kernels_gpu.py): operands inside wider buffers whose surroundings are
+"""What the per-element kernel tests share (tests/test_sample_kernels_gpu.py, tests/test_token_kernels_gpu.py, tests/test_norm_kernels_gpu.py,
+tests/test_prior_kernels_gpu.py): operands inside wider buffers whose surroundings are
 watched, the |got - ref| <= bound assertion, and the err / bound ratios each test prints."""
 import torch
 
